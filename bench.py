@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — whole-job throughput of the Mode-S demodulator hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--samples S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--samples S] [--dump-outputs DIR] [--full]
 
 A "step" = one pass of the hot path (IQ -> magnitude -> preamble sweep + bit slicer + CRC ->
 ordered accept walk -> signal power) over one synthetic UC8 2.4 MSps stream that is already
@@ -9,12 +9,16 @@ resident in HBM when the timed region starts (BASELINE.json configs[1]: single U
 --fix).  With N > 1 every rank demodulates its own independent stream (configs[3]) and the
 decoded message counts/records are gathered over RCCL inside the timed step.
 
-Prints ONE JSON line (rank 0): metric/value/unit as BASELINE.json, plus
+A plain run sets up, warms up, times K steps, writes the last step's outputs (--dump-outputs) and
+prints ONE JSON line (rank 0): metric/value/unit/ms_per_step as BASELINE.json, stage_ms and
   roofline     — k_sweep_uc8 (UC8 converter and preamble sweep in one kernel, round 6): algorithmic bytes (2 B of IQ read + 2 B of
                  magnitude written per sample) / its HIP-event time; with the two kernels (SC16 input, Mode A/C) k_sweep: 2 B per
                  magnitude sample.  `kernels` carries the same figure for k_slice (slicer + CRC + scoring, the longer of the two)
+--full adds what takes runs of its own:
+  the timing events' own constant (k_spin calibration) and the per-launch figures with it taken off,
   cpu_baseline — the reference's own C files (oracle/_ref) timed on this host on the same stream,
-                 whose message list must be bit-identical to the GPU's (checked in the same run).
+                 whose message list must be bit-identical to the GPU's (checked in the same run),
+  pcie_inclusive_msamples_s, and the `configs` dict (the other BASELINE configurations, each checked against the reference).
 """
 import os
 # The HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4).  With torch's and RCCL's
@@ -185,6 +189,33 @@ def emit(out):
     except Exception:
         pass
     print(json.dumps(out), flush=True)
+
+
+DUMP_BUDGET_BYTES = 60_000_000     # --dump-outputs: at most 64 MB in all
+DUMP_SEED = 20251016               # the sample of the records when a feed has more of them than the budget holds
+DUMP_WIDE = ("timestamp", "sysTimestamp", "sig_sumsq", "addr")     # float64 (exact below 2^53); the narrower fields float32
+
+
+def dump_outputs(out_dir, msgs, counters):
+    """--dump-outputs: a feed's message records and the stream's counters as the caller of the feed path receives them, one
+    DIR/<name>.npy per field (`msg_<field>`: one row per record, the 14 message / raw bytes as columns; `counter_<name>`).
+    `msg_count` is the feed's number of records; if they do not all fit in the budget, a fixed seeded sample of them is
+    written and `msg_index` says which (it always does)."""
+    os.makedirs(out_dir, exist_ok=True)
+    per_msg = 8 + sum((8 if f in DUMP_WIDE else 4) * int(np.prod(msgs.dtype[f].shape)) for f in msgs.dtype.names)
+    n = len(msgs)
+    keep = min(n, (DUMP_BUDGET_BYTES - (1 << 16)) // per_msg)
+    idx = np.arange(n) if keep == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+    sel = msgs[idx]
+
+    def put(name, a):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    put("msg_count", np.array([n], dtype=np.float64))
+    put("msg_index", idx.astype(np.float64))
+    for f in msgs.dtype.names:
+        put("msg_" + f, sel[f].astype(np.float64 if f in DUMP_WIDE else np.float32))
+    for k, v in counters.items():
+        put("counter_" + k, np.atleast_1d(np.asarray(v, dtype=np.float64)))
 
 
 def cpu_reference(iq, nsamples, fmt=0, nfix=1, fixdf=1, thr=58):
@@ -592,7 +623,9 @@ def bench_config5(args, rank, local_rank, world):
                                                     "with the GPU to itself; the all-gathers are lists, the final gather is not timed (bytes given)"}
 
     if rank == 0:
-        if not args.no_cpu_baseline:
+        if args.dump_outputs:                    # the capture's messages and counters (one rank: the same feeds as timed, run once more)
+            dump_outputs(args.dump_outputs, msgs, counters)
+        if args.full and not args.no_cpu_baseline:
             iq = helpers.synth(nsamples=n, seed=5150, rate=8000.0, dense=1, threads=min(64, os.cpu_count() or 8)) if (world > 1 or lo != 0 or last != n) else mine
             kind, ref_msgs, st = cpu_reference(iq, n, 0, 2, 1, 58)
             helpers.assert_same_messages(msgs, ref_msgs)
@@ -687,8 +720,13 @@ def main():
     ap.add_argument("--config5-form", choices=["stream", "packets"], default="stream",
                     help="--emulate-ranks: `stream` = every rank's pass through the ordinary pipeline, the schedule from a pre-pass over the expiry "
                          "windows (walk and build overlap the kernels); `packets` = GPU pass first, then the walk of its packets")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true", help="skip the `configs` dict (other BASELINE configurations / input statistics)")
+    ap.add_argument("--full", action="store_true", help="beyond the headline: the timing events' calibration, the in-run check against the "
+                    "reference with the CPU baseline, the PCIe-inclusive rate and the extra configurations (off: the run does only what the "
+                    "headline figure needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path returned for the "
+                    "last feed of its last step (message records field by field, counters) as DIR/<name>.npy in float64 / float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the check against the reference and the CPU baseline")
+    ap.add_argument("--no-extra-configs", action="store_true", help="--full without the `configs` dict (other BASELINE configurations / input statistics)")
     ap.add_argument("--extra-samples", type=int, default=4096 * BUF, help="samples per segment of the extra configurations (default: the headline step)")
     ap.add_argument("--main-cpu", type=int, default=-1, help="experiment: pin the calling thread to this CPU after the context exists")
     ap.add_argument("--exercise-gather", action="store_true", help="run the N>1 aggregator exchange even with one rank (needs torchrun env)")
@@ -866,8 +904,17 @@ def main():
     if os.environ.get("MGPU_DBG_BENCH"):
         sys.stderr.write(f"dbg bench rank {rank}: main thread, warm-up + timed steps: {dbg_t}\n")
     tm = d.timing()                             # sums over the timed region's launches (everything since the last drain)
-    # what two timing events around one kernel report beyond the kernel (include/modes_gpu.h): measured here, or taken from an earlier run
-    bracket_us = args.event_bracket_us if args.event_bracket_us is not None else d.event_bracket_us()
+    # the last step's outputs, where its last feed left them: the consumer's array of that feed (N > 1: what the gather brought to rank 0)
+    if args.dump_outputs and rank == 0:
+        if gath is not None:
+            _, per_rank = gath.fetch()
+            last_msgs = np.concatenate(per_rank)
+        else:
+            last_msgs = bufs[(seq + n_timed - 1) % len(bufs)][:nmsgs_last]
+        dump_outputs(args.dump_outputs, last_msgs, counters)
+    # what two timing events around one kernel report beyond the kernel (include/modes_gpu.h): taken from an earlier run, or measured
+    # here (--full: k_spin launches of its own); without it the per-launch figures are the events' raw intervals only
+    bracket_us = args.event_bracket_us if args.event_bracket_us is not None else d.event_bracket_us() if args.full else None
     # the stage events ride on every 15th chunk only (an event costs ~5 us of idle stream): scale the sampled sums to all chunks
     ev_scale = tm["n_chunks"] / max(1, tm["n_timed_chunks"])
     for key in ("convert_ms", "sweep_ms", "slice_ms", "prescreen_ms"):
@@ -899,7 +946,7 @@ def main():
     #      the timed region (deferred, into the consumer's arrays), against the reference's own code on the 2-segment stream, on
     #      one host core per stream — with N streams that is N pinned reference processes side by side ----
     cpu_result = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         d.reset()
         d.set_deferred(True)
         vb = bufs if bufs is not None and dev_to_host else [np.empty(cap, dtype=readsb_amd.MSG_DTYPE) for _ in range(2)]
@@ -956,8 +1003,9 @@ def main():
         # stream that pair reports the kernel + a constant (4.0 us here: mgpu_event_bracket_us measures it in this process with a
         # kernel of known duration), which is taken off — rocprofv3's kernel durations (profiles/r03_kernel_stats.csv) are the check.
         sweep_raw, slice_raw = float(np.mean(sweep_ms)), float(np.mean(slice_ms))
-        sweep = max(sweep_raw - nlaunch * bracket_us * 1e-3, 1e-6)
-        slice_ = max(slice_raw - nlaunch * bracket_us * 1e-3, 1e-6)
+        corrected = bracket_us is not None      # (a plain run does not calibrate: the corrected figures are null there)
+        sweep = max(sweep_raw - nlaunch * bracket_us * 1e-3, 1e-6) if corrected else None
+        slice_ = max(slice_raw - nlaunch * bracket_us * 1e-3, 1e-6) if corrected else None
         # `achieved` / `frac`: from the RAW interval between the two events around the kernel (what rocprofv3's average duration of the
         # same kernel agrees with); the figure with the events' own constant taken off stands beside it (`frac_bracket_corrected`)
         if sweep_raw <= 0 or slice_raw <= 0:     # (cannot happen: the first chunk of every accounting period is a sampled one)
@@ -970,7 +1018,7 @@ def main():
         bytes_per_sample = FUSED_BYTES_PER_SAMPLE if fused else SWEEP_BYTES_PER_SAMPLE
         sweep_name = "k_sweep_uc8" if fused else "k_sweep"
         achieved = n * bytes_per_sample / (sweep_raw * 1e-3) / 1e9
-        achieved_corrected = n * bytes_per_sample / (sweep * 1e-3) / 1e9
+        achieved_corrected = n * bytes_per_sample / (sweep * 1e-3) / 1e9 if corrected else None
         per_launch = int(n * SWEEP_BYTES_PER_SAMPLE / nlaunch)           # (the launch's size in bytes of magnitudes: what the committed summaries were taken on)
         alg_per_launch = int(n * bytes_per_sample / nlaunch)
         # HBM traffic of one launch from the committed rocprofv3 PMC passes of this same command (FETCH_SIZE x2 on
@@ -1006,41 +1054,42 @@ def main():
                          "launches_per_step": nlaunch, "algorithmic_bytes_per_launch": alg_per_launch,
                          "algorithmic_bytes": ("2 B of UC8 IQ read + 2 B of magnitude written per sample (converter and sweep in one kernel)" if fused
                                                else "2 B of magnitude read per position"),
-                         "avg_launch_ms": round(sweep_raw / nlaunch, 4), "avg_launch_ms_bracket_corrected": round(sweep / nlaunch, 4),
-                         "frac_bracket_corrected": round(achieved_corrected / HBM_PEAK_GBS, 4),
-                         "event_bracket_us": round(bracket_us, 2), "launches_timed": int(tm["n_timed_chunks"]),
-                         "valu_issue": valu_issue(sweep_name, sweep / nlaunch, n / nlaunch) if per_launch == PROFILED_LAUNCH_BYTES else None},
+                         "avg_launch_ms": round(sweep_raw / nlaunch, 4), "avg_launch_ms_bracket_corrected": round(sweep / nlaunch, 4) if corrected else None,
+                         "frac_bracket_corrected": round(achieved_corrected / HBM_PEAK_GBS, 4) if corrected else None,
+                         "event_bracket_us": round(bracket_us, 2) if corrected else None, "launches_timed": int(tm["n_timed_chunks"]),
+                         "valu_issue": valu_issue(sweep_name, sweep / nlaunch, n / nlaunch) if corrected and per_launch == PROFILED_LAUNCH_BYTES else None},
             # the other half of what used to be one kernel: slicer + CRC + scoring over k_sweep's candidate lists.  It reads the
             # same 2 B per sample again (tile staging), so the same algorithmic bytes; its work is per candidate, not per byte.
-            "kernels": {"k_slice": {"avg_launch_ms": round(slice_raw / nlaunch, 4), "avg_launch_ms_bracket_corrected": round(slice_ / nlaunch, 4),
+            "kernels": {"k_slice": {"avg_launch_ms": round(slice_raw / nlaunch, 4), "avg_launch_ms_bracket_corrected": round(slice_ / nlaunch, 4) if corrected else None,
                                     "algorithmic_bytes_per_launch": per_launch,
                                     "achieved": round(n * SWEEP_BYTES_PER_SAMPLE / (slice_raw * 1e-3) / 1e9, 1) if slice_raw > 0 else None,
                                     "frac": round(n * SWEEP_BYTES_PER_SAMPLE / (slice_raw * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if slice_raw > 0 else None,
                                     "unit": "GB/s", "traffic": traffic_slice,
-                                    "valu_issue": valu_issue("k_slice", slice_ / nlaunch, n / nlaunch) if per_launch == PROFILED_LAUNCH_BYTES else None}},
+                                    "valu_issue": valu_issue("k_slice", slice_ / nlaunch, n / nlaunch) if corrected and per_launch == PROFILED_LAUNCH_BYTES else None}},
             "synth_gen_s": round(t_gen, 2),
         }
         if per_rank_host is not None:
             out["per_rank_host_ms"] = per_rank_host
         # the boundary handing over HOST buffers (mgpu_feed_iq from page-locked memory): never `value`, see DESIGN.md §4
-        try:
-            d.host_register(iq)
-            rates = []
-            for _ in range(3):
-                d.reset()
-                t1 = time.perf_counter()
-                d.feed_iq(iq)
-                d.finish()
-                pm, _ = d.collect(reuse=True)
-                rates.append(n / (time.perf_counter() - t1) / 1e6)
-            d.host_unregister(iq)
-            out["pcie_inclusive_msamples_s"] = round(max(rates), 1)
-        except Exception as e:                                   # the measurement is informative only
-            out["pcie_inclusive_msamples_s"] = None
-            out["pcie_inclusive_error"] = str(e)[:200]
+        if args.full:
+            try:
+                d.host_register(iq)
+                rates = []
+                for _ in range(3):
+                    d.reset()
+                    t1 = time.perf_counter()
+                    d.feed_iq(iq)
+                    d.finish()
+                    pm, _ = d.collect(reuse=True)
+                    rates.append(n / (time.perf_counter() - t1) / 1e6)
+                d.host_unregister(iq)
+                out["pcie_inclusive_msamples_s"] = round(max(rates), 1)
+            except Exception as e:                               # the measurement is informative only
+                out["pcie_inclusive_msamples_s"] = None
+                out["pcie_inclusive_error"] = str(e)[:200]
         if cpu_result is not None:
             out["cpu_baseline"] = cpu_result
-        if not args.no_extra_configs and not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_extra_configs and not args.no_cpu_baseline and world == 1:
             d.close()
             out["configs"] = {}
             # Every extra configuration in a process of its own (`--extra-only i`): as the third or fourth context of THIS process the

@@ -73,7 +73,7 @@ def test_bench_multi_rank_path_dry_run(built):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29517", os.path.join(helpers.ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--samples", str(96 * 131072), "--dryrun-gloo"], capture_output=True, text=True, timeout=600, env=env, cwd=helpers.ROOT)
+                        "--samples", str(96 * 131072), "--dryrun-gloo", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=helpers.ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)
@@ -87,7 +87,7 @@ def test_bench_config5_two_shards_dry_run(built):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29519", os.path.join(helpers.ROOT, "bench.py"), "--gpus", "2", "--config", "5", "--steps", "2",
-                        "--warmup", "1", "--samples", str(96 * 131072), "--dryrun-gloo"], capture_output=True, text=True, timeout=600, env=env,
+                        "--warmup", "1", "--samples", str(96 * 131072), "--dryrun-gloo", "--full"], capture_output=True, text=True, timeout=600, env=env,
                        cwd=helpers.ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

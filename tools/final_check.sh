@@ -7,4 +7,4 @@ mkdir -p $out
 cd $R
 timeout 1500 python -m pytest tests -m gpu -q -x 2>&1 | tail -6 > $out/gpu_suite_tail.txt; cat $out/gpu_suite_tail.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-timeout 600 python bench.py > $out/bench_default.log 2> $out/bench_default.err; tail -1 $out/bench_default.log | cut -c1-1500; tail -3 $out/bench_default.err
+timeout 600 python bench.py --full > $out/bench_default.log 2> $out/bench_default.err; tail -1 $out/bench_default.log | cut -c1-1500; tail -3 $out/bench_default.err

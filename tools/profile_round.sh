@@ -21,7 +21,7 @@ cd $R
 sha=$(python -c "import bench; print(bench.kernel_source_sha())")
 { echo "# kernel_source_sha: $sha"; python tools/pmc_kernels.py $out/pmc_sq; } > $out/pmc_sq_summary.txt 2>&1
 python tools/pmc_summary.py $(find $out/pmc_fetch -name "*counter_collection.csv" | head -1) $(find $out/pmc_write -name "*counter_collection.csv" | head -1) $out/pmc_hbm.json $sha > /dev/null 2> $out/pmc_hbm.err
-timeout 400 python bench.py --steps 20 --warmup 3 > $out/bench_plain.log 2>&1
+timeout 400 python bench.py --steps 20 --warmup 3 --full > $out/bench_plain.log 2>&1
 # the micro harnesses (make -C tools micro): k_sweep alone over a cold > 1 GiB array (and its stages), instruction issue rates, atomics; k_slice's parts
 for v in "" _s1 _s2 _s3 _d0 _b1 _b4; do timeout 120 tools/micro/sweep_cold$v 1024 5 4 > $out/sweep_cold$v.json 2> $out/sweep_cold$v.err; done   # _d0: generation 6 (contiguous ranges, no dealer); _b1 / _b4: dealt blocks of 1 / 4 steps
 timeout 120 tools/micro/sweep_cold 1024 5 4 0 2000 0 0 0 > $out/sweep_cold_unpaced.json 2>/dev/null
