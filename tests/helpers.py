@@ -109,13 +109,15 @@ def oracle_run(iq, fmt=0, nfix=1, fixdf=1, thr=58, want_mag=False, mode_ac=0, fi
     return (msgs, st[0], mag) if want_mag else (msgs, st[0])
 
 
-def reference_run(iq, fmt=0, nfix=1, fixdf=1, thr=58):
-    """The checker of the -m gpu parity tests on the BASELINE configurations: the reference's OWN objects (oracle/_ref, compiled from
-    /root/reference in place; the prebuilt files travel to the GPU box) where they are there, the restatement otherwise — one hop
-    less between the HIP path and the reference (tests/test_oracle.py pins the restatement to _ref either way)."""
+def reference_run(iq, fmt=0, nfix=1, fixdf=1, thr=58, want_mag=False, mode_ac=0, flip_before=False):
+    """The checker of the -m gpu parity tests: the reference's OWN objects (oracle/_ref, compiled from the reference's C files in
+    place; the prebuilt files travel to the GPU box) where they are there, the restatement otherwise, so that a developer without
+    them can still run the suite (tests/test_oracle.py pins the restatement to _ref either way).  That the objects ARE there on a
+    GPU run is a test of its own (test_gpu_parity.py::test_reference_objects_are_present), so the fallback cannot pass unnoticed.
+    flip_before = the reference program's other start-up order (oracle_run's filter_clock=1; pinned in tests/test_oracle.py)."""
     if have_ref():
-        return ref_run(iq, fmt, nfix, fixdf, thr)
-    return oracle_run(iq, fmt, nfix, fixdf, thr)
+        return ref_run(iq, fmt, nfix, fixdf, thr, want_mag=want_mag, mode_ac=mode_ac, flip_before=flip_before)
+    return oracle_run(iq, fmt, nfix, fixdf, thr, want_mag=want_mag, mode_ac=mode_ac, filter_clock=1 if flip_before else 0)
 
 
 def oracle_convert(iq, fmt):

@@ -26,7 +26,7 @@ def _oracle_stream(msgs):
 def test_beast_stream(built, seconds, rate, dense, nfix, mode_ac, seed):
     import readsb_amd
     iq = helpers.synth(seconds=seconds, seed=seed, rate=rate, dense=dense, threads=8)
-    want_msgs, _ = helpers.oracle_run(iq, 0, nfix, 1, 58, mode_ac=mode_ac)
+    want_msgs, _ = helpers.reference_run(iq, 0, nfix, 1, 58, mode_ac=mode_ac)
     want = _oracle_stream(want_msgs)
     d = readsb_amd.Demodulator(nfix_crc=nfix, mode_ac=mode_ac, startup_time_ms=helpers.STARTUP_MS, max_samples=len(iq) // 2)
     try:
@@ -101,7 +101,7 @@ def test_beast_stream_in_device_memory(built):
     hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     hip.hipFree.argtypes = [C.c_void_p]
     iq = helpers.synth(seconds=2.0, seed=99, rate=1500.0)
-    want_msgs, _ = helpers.oracle_run(iq)
+    want_msgs, _ = helpers.reference_run(iq)
     d = readsb_amd.Demodulator(startup_time_ms=helpers.STARTUP_MS, max_samples=len(iq) // 2)
     d_in, d_out = C.c_void_p(), C.c_void_p()
     try:

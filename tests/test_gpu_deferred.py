@@ -26,7 +26,7 @@ def test_deferred_feeds_equal_synchronous_feeds(built, external, monkeypatch):
     monkeypatch.setattr(readsb_amd.binding, "DEFAULT_CHUNK_BUFFERS", 16)             # several pipeline chunks per feed
     sizes = [40 * B, 56 * B, 24 * B, 33 * B + 4321]            # several 16-buffer chunks per feed; the last block ends the stream short
     iq = helpers.synth(nsamples=sum(sizes), seed=909, rate=3000.0)
-    want, wst = helpers.oracle_run(iq, 0, 2, 1, 58)
+    want, wst = helpers.reference_run(iq, 0, 2, 1, 58)
     blocks = _blocks(iq, sizes)
 
     # synchronous reference run of the library itself: per-feed message lists
@@ -89,7 +89,7 @@ def test_device_messages_equal_host_messages(built, monkeypatch):
     monkeypatch.setattr(readsb_amd.binding, "DEFAULT_CHUNK_BUFFERS", 16)
     sizes = [48 * B, 40 * B, 19 * B + 999]
     iq = helpers.synth(nsamples=sum(sizes), seed=1234, rate=3500.0)
-    want, wst = helpers.oracle_run(iq, 0, 2, 1, 58)
+    want, wst = helpers.reference_run(iq, 0, 2, 1, 58)
     blocks = _blocks(iq, sizes)
     host = []
     d = readsb_amd.Demodulator(nfix_crc=2, startup_time_ms=helpers.STARTUP_MS, max_samples=64 * B)
@@ -138,7 +138,7 @@ def test_device_built_messages_delivered_to_a_page_locked_array(built, monkeypat
     monkeypatch.setattr(readsb_amd.binding, "DEFAULT_CHUNK_BUFFERS", 16)
     sizes = [48 * B, 40 * B, 19 * B + 999]
     iq = helpers.synth(nsamples=sum(sizes), seed=4321, rate=3500.0)
-    want, wst = helpers.oracle_run(iq, 0, 1, 1, 58)
+    want, wst = helpers.reference_run(iq, 0, 1, 1, 58)
     blocks = _blocks(iq, sizes)
     d = readsb_amd.Demodulator(nfix_crc=1, startup_time_ms=helpers.STARTUP_MS, max_samples=64 * B)
     d.set_deferred(True)
@@ -182,7 +182,7 @@ def test_device_messages_into_the_callers_device_buffer(built, monkeypatch):
     hip.hipFree.argtypes = [C.c_void_p]
     sizes = [40 * B, 33 * B]
     iq = helpers.synth(nsamples=sum(sizes), seed=99, rate=3000.0)
-    want, _ = helpers.oracle_run(iq)
+    want, _ = helpers.reference_run(iq)
     blocks = _blocks(iq, sizes)
     d = readsb_amd.Demodulator(startup_time_ms=helpers.STARTUP_MS, max_samples=64 * B)
     d_buf = C.c_void_p()
@@ -221,7 +221,7 @@ def test_one_chunk_host_feeds_on_a_busy_gpu(built, monkeypatch):
     monkeypatch.setattr(readsb_amd.binding, "DEFAULT_CHUNK_BUFFERS", 64)
     nfeeds, per = 12, 48 * B                                   # one chunk per feed
     iq = helpers.synth(nsamples=nfeeds * per, seed=31337, rate=4000.0)
-    want, wst = helpers.oracle_run(iq, 0, 1, 1, 58)
+    want, wst = helpers.reference_run(iq, 0, 1, 1, 58)
 
     stop = threading.Event()
 

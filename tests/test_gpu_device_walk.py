@@ -24,7 +24,7 @@ sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
 import helpers, readsb_amd
 nfix, rate, dense, seconds, seed, chunk_buffers = {params!r}
 iq = helpers.synth(seconds=seconds, seed=seed, rate=rate, dense=dense, threads=16)
-want, wst = helpers.oracle_run(iq, 0, nfix, 1, 58)
+want, wst = helpers.reference_run(iq, 0, nfix, 1, 58)
 d = readsb_amd.Demodulator(startup_time_ms=helpers.STARTUP_MS, max_samples=max(len(iq) // 2, 131072), nfix_crc=nfix, chunk_buffers=chunk_buffers or 0)
 got, cnt = d.demodulate_capture(iq)
 st = d.device_walk_stats()

@@ -24,7 +24,7 @@ def test_streams_are_independent_and_exact(built, tmp_path):
         path = tmp_path / f"cap{k}.iq"
         iq.tofile(path)
         args += ["--iformat", helpers.FMT_NAMES[fmt], "--ifile", str(path)]
-        msgs, st = helpers.oracle_run(iq, fmt, 1, 1, 58)
+        msgs, st = helpers.reference_run(iq, fmt, 1, 1, 58)
         want.append((_expected_lines(msgs), st))
     prefix = tmp_path / "out"
     r = subprocess.run([CLI] + args + ["--fix", "--out-prefix", str(prefix), "--stats", "--gpu-chunk-buffers", "5"],

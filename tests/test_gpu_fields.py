@@ -98,7 +98,7 @@ def test_stream_messages(built):
         got = d.decode_fields(msgs).view(fu.FIELDS)
     finally:
         d.close()
-    want_msgs, _ = helpers.oracle_run(iq, 0, 2, 1, 58, mode_ac=1)
+    want_msgs, _ = helpers.reference_run(iq, 0, 2, 1, 58, mode_ac=1)
     assert len(msgs) == len(want_msgs) and (msgs["msgbits"] == 16).any()
     want = fu.oracle_fields(np.ascontiguousarray(want_msgs["msg"]), want_msgs["msgbits"].astype(np.int32))
     assert got.tobytes() == want.tobytes()

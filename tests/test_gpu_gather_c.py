@@ -20,7 +20,7 @@ def test_c_gather_single_rank_writes_the_reference_beast_stream(built, tmp_path)
     iq = helpers.synth(seconds=4.0, seed=515, rate=3000.0)
     path, out, idf = tmp_path / "cap.iq", tmp_path / "beast.bin", tmp_path / "nccl.id"
     iq.tofile(path)
-    want, _ = helpers.oracle_run(iq, 0, 2, 1, 58)
+    want, _ = helpers.reference_run(iq, 0, 2, 1, 58)
     r = subprocess.run([EXE, "--rank", "0", "--world", "1", "--id-file", str(idf), "--ifile", str(path), "--aggressive",
                         "--startup-time-ms", str(helpers.STARTUP_MS), "--out", str(out)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
@@ -50,7 +50,7 @@ def test_c_gather_forward_only_is_what_the_reference_program_forwards(built, tmp
     assert "forwarded frames only" in r.stderr
     gold = open(os.path.join(helpers.GOLDEN_DIR, f"beast_{name}.bin"), "rb").read()
     fwd = gu.golden_forwarded(name)
-    msgs, _ = helpers.oracle_run(iq, 0, opt["nfix"], 1, 58)
+    msgs, _ = helpers.reference_run(iq, 0, opt["nfix"], 1, 58)
     deferred = np.fromfile(dfile, dtype="<u8").reshape(-1, 3)
     lib = helpers.oracle_lib()
     lib.modes_oracle_beast_frame.restype = C.c_size_t

@@ -24,7 +24,7 @@ def test_cli_matches_reference_raw_output(built, tmp_path, fmt, flag, nfix):
     iq = helpers.synth(seconds=3.0, seed=77, fmt=fmt)
     path = tmp_path / "cap.iq"
     iq.tofile(path)
-    want, wst = helpers.oracle_run(iq, fmt, nfix, 1, 58)
+    want, wst = helpers.reference_run(iq, fmt, nfix, 1, 58)
     r = subprocess.run([CLI, "--device-type", "ifile", "--ifile", str(path), "--iformat", helpers.FMT_NAMES[fmt], flag,
                         "--raw", "--mlat", "--stats", "--gpu-chunk-buffers", "7"], capture_output=True, text=True, check=True)
     got = r.stdout.strip().splitlines()

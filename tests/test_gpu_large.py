@@ -25,7 +25,7 @@ def _run(iq, **kw):
 ])
 def test_multi_chunk_capture(built, fmt, nfix, fixdf, thr, rate, dense, seconds, seed):
     iq = helpers.synth(seconds=seconds, fmt=fmt, seed=seed, rate=rate, dense=dense, threads=16)
-    want, wst = helpers.oracle_run(iq, fmt, nfix, fixdf, thr)
+    want, wst = helpers.reference_run(iq, fmt, nfix, fixdf, thr)
     got, cnt = _run(iq, fmt=fmt, nfix_crc=nfix, fix_df=fixdf, preamble_threshold=thr)
     assert len(want) > 50000
     helpers.assert_same_messages(got, want)

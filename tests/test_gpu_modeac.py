@@ -21,7 +21,7 @@ def _run(iq, **kw):
 @pytest.mark.parametrize("seconds,rate,seed,nfix", [(3.0, 800.0, 404, 1), (2.0, 300.0, 405, 2), (60.0, 700.0, 406, 1)])
 def test_mode_ac_beside_mode_s(built, seconds, rate, seed, nfix):
     iq = helpers.synth(seconds=seconds, seed=seed, rate=rate, dense=2, threads=16)
-    want, wst = helpers.oracle_run(iq, 0, nfix, 1, 58, mode_ac=1)
+    want, wst = helpers.reference_run(iq, 0, nfix, 1, 58, mode_ac=1)
     got, cnt = _run(iq, nfix_crc=nfix)
     nac = int((want["msgtype"] == 77).sum())
     assert nac > 200 and (want["msgtype"] != 77).sum() > 200
@@ -33,7 +33,7 @@ def test_mode_ac_beside_mode_s(built, seconds, rate, seed, nfix):
 def test_mode_ac_off_is_the_default(built):
     import readsb_amd
     iq = helpers.synth(seconds=2.0, seed=404, rate=800.0, dense=2)
-    want, wst = helpers.oracle_run(iq)                      # no Mode A/C
+    want, wst = helpers.reference_run(iq)                      # no Mode A/C
     d = readsb_amd.Demodulator(startup_time_ms=helpers.STARTUP_MS, max_samples=len(iq) // 2)
     got, cnt = d.demodulate_capture(iq)
     d.close()
@@ -48,7 +48,7 @@ def test_mag_buf_entry_with_mode_ac(built):
     import readsb_amd
     B, TR = 131072, 326
     iq = helpers.synth(nsamples=6 * B + 50000, seed=97, rate=700.0, dense=2)
-    want, wst, mag = helpers.oracle_run(iq, 0, 1, 1, 58, want_mag=True, mode_ac=1)
+    want, wst, mag = helpers.reference_run(iq, 0, 1, 1, 58, want_mag=True, mode_ac=1)
     assert (want["msgbits"] == 16).sum() > 20
     n = iq.size // 2
     d = readsb_amd.Demodulator(mode_ac=1, startup_time_ms=helpers.STARTUP_MS, max_samples=B)
@@ -80,7 +80,7 @@ def test_mode_ac_on_the_sc16_formats(built, fmt, seconds, rate, seed):
     the reference's converters accumulate as sequential FLOAT sums (convert.c:225-249, 342-366) — reproduced bit for bit
     (k_fsum_sc16), so the replies and every counter, the noise power sums included, equal the reference's."""
     iq = helpers.synth(seconds=seconds, seed=seed, rate=rate, dense=2, fmt=fmt, threads=16)
-    want, wst = helpers.oracle_run(iq, fmt, 1, 1, 58, mode_ac=1)
+    want, wst = helpers.reference_run(iq, fmt, 1, 1, 58, mode_ac=1)
     got, cnt = _run(iq, fmt=fmt)
     nac = int((want["msgtype"] == 77).sum())
     assert nac > 100 and (want["msgtype"] != 77).sum() > 100

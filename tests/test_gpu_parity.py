@@ -1,5 +1,5 @@
-"""-m gpu: the HIP path (through the C ABI) against the CPU oracle on the same seeded captures — on the BASELINE configurations
-(test_uc8_options, test_uc8_10s_config2, test_dense_bursts) against the reference's own objects (oracle/_ref) where they are present.
+"""-m gpu: the HIP path (through the C ABI) against the reference's own objects (oracle/_ref, helpers.reference_run) on the same
+seeded captures; test_reference_objects_are_present fails where they are missing.
 Bit-exact bar: every accepted message (timestamp, frame bytes raw and corrected, score,
 corrected bits, address, signal level) and every demod counter."""
 import numpy as np
@@ -8,6 +8,19 @@ import pytest
 import helpers
 
 pytestmark = pytest.mark.gpu
+
+
+def test_reference_objects_are_present():
+    """The checker of this suite is the reference's own code (oracle/_ref/ref_demod, built beside the library and carried to the GPU
+    machine).  helpers.reference_run falls back to the restatement without it, so that a developer without the reference can work;
+    a GPU run without it has not consulted the reference once, and that is a failure, not a skip."""
+    assert helpers.have_ref(), f"{helpers.REF_BIN} is missing: the -m gpu tests would compare with the restatement only"
+    iq = helpers.synth(nsamples=200000, seed=3, rate=4000.0)
+    a, sa = helpers.ref_run(iq)
+    b, sb = helpers.oracle_run(iq)
+    assert len(a) > 50 and a.tobytes() == b.tobytes()        # ... and it runs here
+    for f in helpers.COUNTER_FIELDS:
+        assert np.array_equal(np.asarray(sa[f]), np.asarray(sb[f])), f
 
 
 def _demod(iq, **kw):
@@ -60,7 +73,7 @@ def test_uc8_10s_config2(built):
 def test_chunked_feeds_equal_single_feed(built):
     """Feeding the stream in several calls (tail + filter state carried) changes nothing."""
     iq = helpers.synth(seconds=4.0, seed=5)
-    want, wst = helpers.oracle_run(iq)
+    want, wst = helpers.reference_run(iq)
     import readsb_amd
     d = readsb_amd.Demodulator(startup_time_ms=helpers.STARTUP_MS, max_samples=8 * 131072)
     got, cnt = d.demodulate_capture(iq, chunk_samples=3 * 131072)
@@ -82,7 +95,7 @@ def test_dense_bursts(built):
 def test_edge_lengths(built, nsamples):
     """Empty, tiny, exactly-one-buffer (extra zero-length buffer at EOF) and ragged captures."""
     iq = helpers.synth(nsamples=nsamples, seed=3, rate=4000.0)
-    want, wst = helpers.oracle_run(iq)
+    want, wst = helpers.reference_run(iq)
     got, cnt, _ = _demod(iq)
     helpers.assert_same_messages(got, want)
     helpers.assert_same_counters(cnt, wst)
@@ -90,7 +103,7 @@ def test_edge_lengths(built, nsamples):
 
 def test_noise_only(built):
     iq = helpers.synth(seconds=1.0, seed=9, rate=0.0)
-    want, wst = helpers.oracle_run(iq)
+    want, wst = helpers.reference_run(iq)
     got, cnt, _ = _demod(iq)
     helpers.assert_same_messages(got, want)
     helpers.assert_same_counters(cnt, wst)
@@ -101,7 +114,7 @@ def test_caller_message_buffer(built):
     fails loudly instead of dropping messages."""
     import readsb_amd
     iq = helpers.synth(seconds=3.0, seed=77)
-    want, wst = helpers.oracle_run(iq)
+    want, wst = helpers.reference_run(iq)
     d = readsb_amd.Demodulator(startup_time_ms=helpers.STARTUP_MS, max_samples=64 * 131072)
     try:
         buf = np.empty(len(want) + 100, dtype=readsb_amd.MSG_DTYPE)

@@ -23,7 +23,7 @@ def test_messages_fields_and_beast_frames_without_leaving_the_device(built, monk
     hip.hipFree.argtypes = [C.c_void_p]
     sizes = [40 * B, 35 * B + 17]
     iq = helpers.synth(nsamples=sum(sizes), seed=777, rate=3000.0)
-    want, _ = helpers.oracle_run(iq, 0, 1, 1, 58)
+    want, _ = helpers.reference_run(iq, 0, 1, 1, 58)
     lib = helpers.oracle_lib()
     lib.modes_oracle_beast_frame.restype = C.c_size_t
     lib.modes_oracle_beast_frame.argtypes = [C.c_void_p, C.c_void_p]

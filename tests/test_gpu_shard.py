@@ -23,7 +23,7 @@ def test_sharded_capture_equals_unsharded(built, nshards, seconds, dense, rate, 
     iq = helpers.synth(seconds=seconds, seed=900 + nshards + int(seconds), rate=rate, dense=dense, threads=16)
     if seconds > 200:
         assert shard.warmup_start(shard.shard_ranges(iq.size // 2, nshards)[-1][0]) > 0     # the cutoff is exercised
-    want, wst = helpers.oracle_run(iq, 0, nfix, 1, 58)
+    want, wst = helpers.reference_run(iq, 0, nfix, 1, 58)
     d = readsb_amd.Demodulator(nfix_crc=nfix, startup_time_ms=helpers.STARTUP_MS, max_samples=256 * 131072)
     try:
         got, cnt = demodulate_sharded_local(d, iq, nshards)
@@ -43,7 +43,7 @@ def test_sharded_walk_equals_unsharded(built, nshards, seconds, dense, rate, nfi
     import readsb_amd
     from readsb_amd import shard
     iq = helpers.synth(seconds=seconds, seed=1900 + nshards + int(seconds), rate=rate, dense=dense, naircraft=naircraft, threads=16)
-    want, wst = helpers.ref_run(iq, 0, nfix, 1, 58) if helpers.have_ref() else helpers.oracle_run(iq, 0, nfix, 1, 58)
+    want, wst = helpers.reference_run(iq, 0, nfix, 1, 58)
     d = readsb_amd.Demodulator(nfix_crc=nfix, startup_time_ms=helpers.STARTUP_MS, max_samples=256 * 131072)
     stats = {}
     try:
@@ -69,7 +69,7 @@ def test_sharded_stream_equals_unsharded(built, nshards, seconds, dense, rate, n
     import readsb_amd
     from readsb_amd import shard
     iq = helpers.synth(seconds=seconds, seed=2900 + nshards + int(seconds), rate=rate, dense=dense, naircraft=naircraft, threads=16)
-    want, wst = helpers.ref_run(iq, 0, nfix, 1, 58) if helpers.have_ref() else helpers.oracle_run(iq, 0, nfix, 1, 58)
+    want, wst = helpers.reference_run(iq, 0, nfix, 1, 58)
     # (deferred: a feed call must hold a whole warm-up — up to 120 s + a buffer — or a whole range)
     d = readsb_amd.Demodulator(nfix_crc=nfix, startup_time_ms=helpers.STARTUP_MS, max_samples=(4096 if deferred else 256) * 131072)
     stats = {}
@@ -102,7 +102,7 @@ def _rank_walk(rank, world, port, q, seconds, seed, form="packets"):
     d.close()
     ok = True
     if rank == 0:
-        want, wst = helpers.oracle_run(iq)
+        want, wst = helpers.reference_run(iq)
         got, cnt = res
         try:
             helpers.assert_same_messages(got, want)
@@ -149,7 +149,7 @@ def _rank(rank, world, port, q, seconds, seed):
     d.close()
     ok = True
     if rank == 0:
-        want, wst = helpers.oracle_run(iq)
+        want, wst = helpers.reference_run(iq)
         got, cnt = res
         try:
             helpers.assert_same_messages(got, want)

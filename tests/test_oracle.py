@@ -44,6 +44,13 @@ def test_restatement_matches_golden(built, name):
     (1, 1, 1, 58, dict(seconds=1.0, seed=35, fmt=1)),
     (0, 1, 1, 58, dict(nsamples=131072, seed=36)),          # exact multiple: zero-length EOF buffer
     (0, 1, 1, 58, dict(nsamples=1000, seed=37)),
+    # hostile density (tests/test_gpu_density.py): Gaussian noise of 12 / 25 LSB at the lowest threshold, 48-62 preambles per 1000
+    # samples in the reference, with overlapping DF17 bursts (dense bit 0) and Mode A/C replies as FRUIT (bit 1) on top
+    (0, 2, 1, 40, dict(seconds=2.0, seed=71, rate=2000.0, dense=4, noise=12.0)),
+    (0, 2, 1, 40, dict(seconds=2.0, seed=72, rate=20000.0, dense=6, noise=12.0)),
+    (0, 2, 1, 40, dict(seconds=2.0, seed=73, rate=20000.0, dense=7, noise=12.0)),
+    (2, 2, 1, 40, dict(seconds=2.0, seed=74, rate=8000.0, dense=7, noise=25.0, fmt=2)),
+    (1, 2, 1, 40, dict(seconds=2.0, seed=75, rate=8000.0, dense=7, noise=12.0, fmt=1)),
 ])
 def test_restatement_matches_reference_live(built, fmt, nfix, fixdf, thr, skw):
     iq = helpers.synth(**skw)
@@ -56,6 +63,24 @@ def test_restatement_matches_reference_live(built, fmt, nfix, fixdf, thr, skw):
     for f in ("signal_power_sum", "peak_signal_power", "noise_power_sum"):
         x, y = float(sa[f]), float(sb[f])
         assert (np.isnan(x) and np.isnan(y)) or x == y
+
+
+@pytest.mark.skipif(not helpers.have_ref(), reason="oracle/_ref not built")
+@pytest.mark.parametrize("mode_ac", [0, 1])
+def test_filter_clock_1_is_the_references_flip_before(built, mode_ac):
+    """helpers.reference_run maps oracle_run's filter_clock=1 to ref_run's flip_before=True (the reference program's other start-up
+    order: the first icaoFilterExpire() before buffer 0).  70 s, so that the second expiry falls inside the capture as well, and
+    the two orders give different lists (else the mapping would be pinned by nothing)."""
+    iq = helpers.synth(seconds=70.0, seed=61, rate=600.0, dense=2 if mode_ac else 0, threads=16)
+    a, sa = helpers.oracle_run(iq, mode_ac=mode_ac, filter_clock=1)
+    b, sb = helpers.ref_run(iq, mode_ac=mode_ac, flip_before=True)
+    c, _ = helpers.ref_run(iq, mode_ac=mode_ac)
+    assert a.tobytes() == b.tobytes() and len(a) > 10000
+    assert b.tobytes() != c.tobytes()
+    for f in helpers.COUNTER_FIELDS:
+        assert np.array_equal(np.asarray(sa[f]), np.asarray(sb[f])), f
+    for f in ("signal_power_sum", "peak_signal_power", "noise_power_sum"):
+        assert float(sa[f]) == float(sb[f]), f
 
 
 @pytest.mark.skipif(not helpers.have_ref(), reason="oracle/_ref not built")
