@@ -595,6 +595,16 @@ class Demodulator:
         self._chk(self.lib.mgpu_beast_encode_device(self.ctx, C.c_void_p(d_msgs_ptr), n, C.c_void_p(d_out_ptr), cap, C.byref(nb)), "mgpu_beast_encode_device")
         return int(nb.value)
 
+    def beast_encode_gated_device(self, d_msgs_ptr, d_verdict_ptr, n, d_out_ptr, cap, d_deferred_ptr, deferred_cap, net_rule=False):
+        """mgpu_beast_encode_gated_device: the caller's verdict bytes applied to records in HBM, stream and deferred[] list written to
+        HBM; returns (the stream's size in bytes, the number of deferred messages)."""
+        nb, nd = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self.lib.mgpu_beast_encode_gated_device(self.ctx, C.c_void_p(d_msgs_ptr), C.c_void_p(d_verdict_ptr), C.c_uint64(n),
+                                                          C.c_uint32(1 if net_rule else 0), C.c_void_p(d_out_ptr), C.c_uint64(cap), C.byref(nb),
+                                                          C.c_void_p(d_deferred_ptr), C.c_uint64(deferred_cap), C.byref(nd)),
+                  "mgpu_beast_encode_gated_device")
+        return int(nb.value), int(nd.value)
+
     def host_cpus(self):
         """CPUs the context's host threads are pinned to (empty list: not pinned)."""
         buf = (C.c_int32 * 64)()

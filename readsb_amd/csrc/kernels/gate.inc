@@ -207,7 +207,9 @@ __global__ __launch_bounds__(kBlock) void k_gate_walk(const uint64_t *keys, uint
             GateInfo g1 = {0, 0, 0};
             if (cnt == WAVE && (uint32_t) (key1 >> 32) == addr) g1 = info[(uint32_t) key1];
             const long long now = g.now;
-            const bool rel = mine && (g.flags & GT_RELIABLE), cpr = mine && (g.flags & GT_CPR);
+            // a position message counts as one only with a reliable address (the aircraft's copy is kept, and cpr_first set, behind the
+            // lookup that drops the others: track.c:1905-1921).  The field decode sets the flag on DF17 / DF18 alone; a caller's records need not
+            const bool rel = mine && (g.flags & GT_RELIABLE), cpr = rel && (g.flags & GT_CPR);
             const uint64_t mr = __ballot(rel), mn = __ballot(rel && !cpr), mc = __ballot(cpr);
             // the last reliable / reliable non-position message below this lane, the first position message of all
             const uint64_t pr = mr & lt_mask, pn = mn & lt_mask;

@@ -67,10 +67,12 @@ def oracle_gate_raw(msgtype, addr, iid, cb, cpr, now_ms, buffer):
     return out
 
 
-def synthetic_list(n, seconds, naircraft, seed, startup_ms=helpers.STARTUP_MS if hasattr(helpers, "STARTUP_MS") else 0):
+def synthetic_list(n, seconds, naircraft, seed, startup_ms=helpers.STARTUP_MS if hasattr(helpers, "STARTUP_MS") else 0, cpr_unreliable=0.0):
     """A message list that never saw a sample: what the gate reads of mgpu_msg / mgpu_fields (timestamp on the ifile grid, sysTimestamp,
     msgtype, correctedbits; addr, IID, the CPR flag) for `naircraft` aircraft over `seconds` — long gaps, hours of life, non-ICAO
-    addresses, Address/Parity formats with address 0, bursts of more than 256 messages in a buffer."""
+    addresses, Address/Parity formats with address 0, bursts of more than 256 messages in a buffer.
+    cpr_unreliable: the share of the messages WITHOUT a reliable address (DF4 / DF20, DF11 with IID != 0) that carry the CPR flag all
+    the same — the field decode never sets it there, mgpu_track_gate_device takes the records from the caller."""
     import readsb_amd
     rng = np.random.default_rng(seed)
     pos = np.sort(rng.integers(0, int(seconds * 2.4e6), size=n)).astype(np.int64)
@@ -92,6 +94,8 @@ def synthetic_list(n, seconds, naircraft, seed, startup_ms=helpers.STARTUP_MS if
     cb = np.select([rng.random(n) < 0.85, rng.random(n) < 0.7], [0, 1], 2).astype(np.uint8)
     msgs = np.zeros(n, dtype=readsb_amd.MSG_DTYPE)
     msgs["timestamp"] = pos * 5 + 768 + rng.integers(4, 9, size=n)
+    if cpr_unreliable:                                                                # (drawn last: the lists without it stay what they were)
+        cpr[((msgtype == 4) | (msgtype == 20) | ((msgtype == 11) & (iid != 0))) & (rng.random(n) < cpr_unreliable)] = 1
     msgs["sysTimestamp"] = startup_ms + msgs["timestamp"] // 12000
     msgs["msgtype"], msgs["correctedbits"], msgs["msgbits"], msgs["addr"] = msgtype, cb, np.where(msgtype >= 16, 112, 56), addr
     fields = np.zeros(n, dtype=readsb_amd.FIELDS_DTYPE)

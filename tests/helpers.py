@@ -195,3 +195,22 @@ def assert_same_counters(gpu_counters, oracle_stats, float_tol=0.0):
             assert a == b, f"{f}: gpu {a!r} != oracle {b!r}"
         else:
             assert abs(a - b) <= float_tol * max(1.0, abs(b)), f"{f}: gpu {a!r} vs oracle {b!r}"
+
+
+def beast_frames(stream):
+    """Split a beast byte stream into raw frames and their unescaped fields (type, 48-bit timestamp, sig, message)."""
+    out, i, n = [], 0, len(stream)
+    while i < n:
+        assert stream[i] == 0x1A
+        j = i + 2
+        while j < n and not (stream[j] == 0x1A and (j + 1 >= n or stream[j + 1] != 0x1A)):
+            j += 2 if stream[j] == 0x1A else 1
+        raw = bytes(stream[i:j])
+        body = raw[2:].replace(b"\x1a\x1a", b"\x1a")
+        out.append((raw, raw[1], int.from_bytes(body[:6], "big"), body[6], body[7:]))
+        i = j
+    return out
+
+
+GOLDEN_BEAST = [("uc8_fix_2s", dict(seconds=2.0, seed=99, rate=1500.0), dict(nfix=1, mode_ac=0)),
+                ("uc8_aggressive_modeac_3s", dict(seconds=3.0, seed=98, rate=700.0, dense=2), dict(nfix=2, mode_ac=1))]

@@ -111,6 +111,29 @@ def test_gate_scans_equal_the_message_by_message_machine(built, n, seconds, nair
     assert ((want & 3) == 2).sum() > 0 and ((want & 3) == 1).sum() > 0 and ((want & 3) == 0).sum() > 0
 
 
+def test_gate_scans_equal_the_machine_with_the_position_flag_on_unreliable_addresses(built):
+    """The first position message starts the position timeout only when its address is reliable (track.c:1917-1921 behind :1905-1915;
+    oracle/modes_oracle_gate.c sets cpr_first in that branch alone).  The field decode sets the CPR flag on DF17 / DF18 only, but
+    mgpu_track_gate_device takes the field records from the caller: with the flag on a third of the DF4 / DF20 / DF11-with-IID
+    messages, over three hours, a walk that takes the time from any flagged message defers messages the machine forwards."""
+    import readsb_amd
+    msgs, fields, raw = gu.synthetic_list(300000, 3 * 3600.0, 40, 5, cpr_unreliable=0.35)
+    unreliable = (raw["msgtype"] == 4) | (raw["msgtype"] == 20) | ((raw["msgtype"] == 11) & (raw["iid"] != 0))
+    assert (raw["cpr"][unreliable] == 1).mean() > 0.3 and (raw["cpr"][unreliable] == 0).mean() > 0.3
+    want = gu.oracle_gate_raw(**raw)
+    # the flag on those messages changes nothing for the machine; a machine that let it start the timeout would differ
+    plain = dict(raw, cpr=np.where(unreliable, 0, raw["cpr"]).astype(np.uint8))
+    assert np.array_equal(want, gu.oracle_gate_raw(**plain))
+    d = readsb_amd.Demodulator(startup_time_ms=helpers.STARTUP_MS, max_samples=1 << 20)
+    try:
+        got = _gate_in_hbm(d, msgs, fields)
+    finally:
+        d.close()
+    bad = np.nonzero(got != want)[0]
+    assert len(bad) == 0, f"{len(bad)} of {len(got)} verdicts differ, first at {bad[:5]}: got {got[bad[:5]]} want {want[bad[:5]]}"
+    assert ((want & 3) == 2).sum() > 0 and ((want & 3) == 1).sum() > 0 and ((want & 3) == 0).sum() > 0
+
+
 def test_position_timeout_defers(built):
     """removeStaleRange deletes an aircraft with a reliable position once that position is an hour old, however recently it was
     heard (track.c:2835-2866): behind it a->messages restarts at 1 and the next corrected-bit message is NOT forwarded.  Whether and

@@ -144,26 +144,7 @@ def test_mode_ac_restatement_equals_reference():
     assert only_s.tobytes() == want[want["msgtype"] != 77].tobytes()
 
 
-def _beast_frames(stream):
-    """Split a beast byte stream into raw frames and their unescaped fields (type, 48-bit timestamp, sig, message)."""
-    out, i, n = [], 0, len(stream)
-    while i < n:
-        assert stream[i] == 0x1A
-        j = i + 2
-        while j < n and not (stream[j] == 0x1A and (j + 1 >= n or stream[j + 1] != 0x1A)):
-            j += 2 if stream[j] == 0x1A else 1
-        raw = bytes(stream[i:j])
-        body = raw[2:].replace(b"\x1a\x1a", b"\x1a")
-        out.append((raw, raw[1], int.from_bytes(body[:6], "big"), body[6], body[7:]))
-        i = j
-    return out
-
-
-GOLDEN_BEAST = [("uc8_fix_2s", dict(seconds=2.0, seed=99, rate=1500.0), dict(nfix=1, mode_ac=0)),
-                ("uc8_aggressive_modeac_3s", dict(seconds=3.0, seed=98, rate=700.0, dense=2), dict(nfix=2, mode_ac=1))]
-
-
-@pytest.mark.parametrize("name,synth_kw,opt", GOLDEN_BEAST)
+@pytest.mark.parametrize("name,synth_kw,opt", helpers.GOLDEN_BEAST)
 def test_beast_frames_equal_the_reference_programs(name, synth_kw, opt):
     """The golden streams were written by the whole reference program (`--dump-beast`, tests/golden/make_beast_golden.py).
     Every frame in them must be byte-identical to the restated encoder's frame for the message with that timestamp —
@@ -171,7 +152,7 @@ def test_beast_frames_equal_the_reference_programs(name, synth_kw, opt):
     message list against the complete reference program rather than the harness."""
     import ctypes as C
     gold = open(os.path.join(helpers.GOLDEN_DIR, f"beast_{name}.bin"), "rb").read()
-    frames = _beast_frames(gold)
+    frames = helpers.beast_frames(gold)
     iq = helpers.synth(**synth_kw)
     msgs, _ = helpers.oracle_run(iq, 0, opt["nfix"], 1, 58, mode_ac=opt["mode_ac"])
     lib = helpers.oracle_lib()
