@@ -877,18 +877,16 @@ void launch_fsum_sc16_wide(int format, const uint8_t *iq, const uint16_t *mag, u
 }
 #endif  // MGPU_EXPERIMENTS
 
-// max_blocks (UC8): the grid's upper bound — 1024 = four workgroups of 33 KB LDS per CU, the stand-alone converter; the side
-// stream's converter (api.cpp) asks for more, shorter-lived workgroups that fill in beside k_slice
-void launch_convert(int format, const ConvertParams &p, hipStream_t s, unsigned max_blocks, int variant) {
+// the grid's upper bound: 1024 = four workgroups of 33 KB LDS per CU
+void launch_convert(int format, const ConvertParams &p, hipStream_t s) {
     if (p.n == 0) return;
     const uint64_t nchunks = (kTrailing + p.n + 7) / 8 - kTrailing / 8;
     uint64_t blocks = (nchunks + kBlock * 8 - 1) / (kBlock * 8);   // >= 8 chunks per thread
     if (blocks < 1) blocks = 1;
-    if (max_blocks == 0) max_blocks = 1024;
-    if (blocks > max_blocks) blocks = max_blocks;
+    if (blocks > 1024) blocks = 1024;
     const bool lean_ok = p.buf_samples % 2048u == 0 && p.buf_samples >= 2048u && p.n < (1ull << 34);
-    if (format == 0 && lean_ok && variant != 1) hipLaunchKernelGGL(k_convert_uc8_lean, dim3((unsigned) blocks), dim3(kBlock), 0, s, p);
-    else if (format == 0) hipLaunchKernelGGL(k_convert_uc8, dim3((unsigned) (blocks > 1024 ? 1024 : blocks)), dim3(kBlock), 0, s, p);
+    if (format == 0 && lean_ok) hipLaunchKernelGGL(k_convert_uc8_lean, dim3((unsigned) blocks), dim3(kBlock), 0, s, p);
+    else if (format == 0) hipLaunchKernelGGL(k_convert_uc8, dim3((unsigned) blocks), dim3(kBlock), 0, s, p);
     else if (format == 1) hipLaunchKernelGGL(k_convert_sc16<15>, dim3((unsigned) blocks * 2), dim3(kBlock), 0, s, p);
     else hipLaunchKernelGGL(k_convert_sc16<11>, dim3((unsigned) blocks * 2), dim3(kBlock), 0, s, p);
 }

@@ -422,7 +422,7 @@ __global__ __launch_bounds__(kBlock, 3) void k_slice(SweepParams p) {
 
 // persistent grid = the workgroups resident at once (occupancy x CUs) for this much dynamic LDS
 // (the 2-bit syndrome keys of --aggressive take 12 KB: three workgroups per CU instead of four)
-unsigned launch_slice(const SweepParams &p, hipStream_t s, unsigned max_blocks) {   // returns its grid size = rows of p.sweep_part written; max_blocks: cap on the grid (0 = none; 768 = three workgroups per CU, room for a converter workgroup beside them)
+unsigned launch_slice(const SweepParams &p, hipStream_t s) {   // returns its grid size = rows of p.sweep_part written
     if (p.nunits == 0) return 0;
     const size_t dyn = ((size_t) p.n_long + p.n_short + 2 * (kKeyBuckets + 1) + 8) / 2 * sizeof(uint32_t);   // halfwords (slicer.inc: key_tables), rounded up to words
     // (per device and table size; two contexts racing here compute the same value twice)
@@ -434,7 +434,7 @@ unsigned launch_slice(const SweepParams &p, hipStream_t s, unsigned max_blocks) 
         e = ((uint64_t) dyn << 32) | resident_grid((const void *) k_slice, dyn, kSweepMaxBlocks);
         cache[dev & 63].store(e, std::memory_order_relaxed);
     }
-    const unsigned cached = max_blocks && max_blocks < (uint32_t) e ? max_blocks : (uint32_t) e;
+    const unsigned cached = (uint32_t) e;
     const unsigned ntiles = (unsigned) ((p.n + kSlTile - 1) / kSlTile);
     const unsigned want = (ntiles + (kBlock / WAVE) - 1) / (kBlock / WAVE);   // at least one tile per wave
     const unsigned blocks = want < cached ? want : cached;

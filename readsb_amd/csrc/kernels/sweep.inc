@@ -46,55 +46,27 @@ static_assert(kUnit % kSwStep == 0 && kSwUnroll < 8 && (kSwHalf * 2) % 16 == 0, 
 #ifndef MGPU_SW_STAGE
 #define MGPU_SW_STAGE 0
 #endif
-// ... and of the threshold rounds: 1 = without the sample gather (junk operands), 2 = gather without the dot products (both: wrong
-// results, timing only); 3 = the gather as six aligned ds_read_b64 + a dword select (results exact); MGPU_SW_NBUF=1: one LDS half,
-// the queue emptied after every step, 8 waves per SIMD (results exact)
-#ifndef MGPU_SW_EXP
-#define MGPU_SW_EXP 0
-#endif
-#ifndef MGPU_SW_NBUF
-#define MGPU_SW_NBUF 2
-#endif
-// MGPU_SW_TOUCH=1: besides the register prefetch of the next step, every lane reads one dword of the step after it (32 bytes apart: the
-// wave touches all sixteen 128-byte lines of those 2 KB), so that a COLD array's lines are on their way from HBM two steps ahead and the
-// real loads, one step ahead, find them in the L2.  The value is never used; it is "consumed" a step later so that the compiler's
-// s_waitcnt counts stay exact.
-#ifndef MGPU_SW_TOUCH
-#define MGPU_SW_TOUCH 0
-#endif
-// MGPU_SW_DEAL=1 (generation 7): a wave takes HALF of its equal share as one contiguous range without asking and the rest from a dealer,
-// two steps at a time (pools of workgroups, one counter per pool, 256 bytes apart: k_slice's dealer, see slice.inc).  With equal
-// contiguous shares (generation 6) the waves of a launch ended between 45 and 63 us of a 63 us kernel (profiles/r04_sweep_cold.json:
-// waves alive 86 %) — VALU issue goes by age, the memory system is not fair, and pacing only narrows the spread.  Nothing in a step
-// depends on which step the wave swept before: the survivors left over from the previous step are evaluated out of the OTHER LDS
-// half whatever its step number was (`s_prev`), so a dealt block needs no flush and no restart.  0 = generation 6's ranges.
-#ifndef MGPU_SW_DEAL
-#define MGPU_SW_DEAL 1
-#endif
-// MGPU_SW_NT_STORE=1: k_sweep_uc8 writes the magnitudes with non-temporal stores (A/B: profiles/r06_sweep_fused.txt)
-#ifndef MGPU_SW_NT_STORE
-#define MGPU_SW_NT_STORE 0
-#endif
-#ifndef MGPU_SW_DEAL_STEPS
-#define MGPU_SW_DEAL_STEPS 2
-#endif
-// MGPU_SW_STATIC_BLOCK=B (round 6): the static half of a wave's share not as ONE contiguous range but as blocks of B steps, block j of
-// wave w = (j * waves + w): at any time the grid's waves work on one contiguous window of the chunk (waves x B steps = 32 MB of
-// samples and as much of magnitudes) instead of 4096 places 32 KB apart.  For k_sweep_uc8 — which sits on its memory time with a
-// 1:1 read / write mix — that is 5 % (bracket 0.414-0.420 against 0.423-0.441 ms per 537 M samples, roofline.frac 0.645 against
-// 0.61, three interleaved sessions, profiles/r06_sweep_fused.txt (7)); B = 8 the same, B = 2 nothing, dealt blocks of 4 / 8 steps
-// or another static share than half: worse.  k_sweep alone (reads only, issue-bound): no difference (cold 65.6 / 65.7 us).
-// 0 = one contiguous range per wave (generations 6-7).
-#ifndef MGPU_SW_STATIC_BLOCK
-#define MGPU_SW_STATIC_BLOCK 4
-#endif
-#ifndef MGPU_SW_STATIC_PCT
-#define MGPU_SW_STATIC_PCT 50                                // ... and the static share of a wave's steps, per cent (the rest is dealt)
-#endif
-constexpr uint32_t kSwDealSteps = MGPU_SW_DEAL_STEPS;        // steps per dealt block
+// Generation 7's dealing: a wave takes HALF of its equal share without asking and the rest from a dealer, two steps at a time (pools
+// of workgroups, one counter per pool, 256 bytes apart: k_slice's dealer, see slice.inc).  With equal contiguous shares (generation 6)
+// the waves of a launch ended between 45 and 63 us of a 63 us kernel (profiles/r04_sweep_cold.json: waves alive 86 %) — VALU issue
+// goes by age, the memory system is not fair, and pacing only narrows the spread.  Nothing in a step depends on which step the wave
+// swept before: the survivors left over from the previous step are evaluated out of the OTHER LDS half whatever its step number was
+// (`s_prev`), so a dealt block needs no flush and no restart.
+// (Measured and dropped: generation 6's contiguous ranges, profiles/r05_sweep_cold_d0.json; an L2 touch two steps ahead, 74.9 us cold,
+// DESIGN.md §3; non-temporal magnitude stores in k_sweep_uc8, profiles/r06_sweep_fused.txt; one LDS half with the queue emptied after
+// every step, 8 waves per SIMD.)
+constexpr uint32_t kSwDealSteps = 2;                         // steps per dealt block (1 and 4 no better: profiles/r05_sweep_cold_b1.json, r05_sweep_cold_b4.json)
+// The static half of a wave's share not as ONE contiguous range but as blocks of kSwStaticBlock steps, block j of wave w =
+// (j * waves + w): at any time the grid's waves work on one contiguous window of the chunk (waves x B steps = 32 MB of samples and
+// as much of magnitudes) instead of 4096 places 32 KB apart.  For k_sweep_uc8 — which sits on its memory time with a 1:1 read /
+// write mix — that is 5 % (bracket 0.414-0.420 against 0.423-0.441 ms per 537 M samples, roofline.frac 0.645 against 0.61, three
+// interleaved sessions, profiles/r06_sweep_fused.txt (7)); B = 8 the same, B = 2 nothing, dealt blocks of 4 / 8 steps or another
+// static share than half: worse.  k_sweep alone (reads only, issue-bound): no difference (cold 65.6 / 65.7 us).
+constexpr uint32_t kSwStaticBlock = 4;                       // steps per static block
+constexpr uint32_t kSwStaticPct = 50;                        // the static share of a wave's steps, per cent (the rest is dealt)
 
 struct SweepLds {                                            // wave-private LDS
-    uint16_t mag[MGPU_SW_NBUF * kSwHalf];                    // 4224 B: two steps, each with its own look-ahead
+    uint16_t mag[2 * kSwHalf];                               // 4224 B: two steps, each with its own look-ahead
     uint16_t pq[kSwPQCap];                                   // 2192 B: pre-check survivors, sample index in mag[] + 1
 };
 
@@ -212,19 +184,11 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, SweepLds *s_w, 
     const uint32_t nwaves = gridDim.x * (BLOCK / WAVE);
     // the wave's share of the chunk's nsteps: the contiguous steps [st_next, st_end) first, then blocks of kSwDealSteps from its pool
     const uint32_t nsteps = (uint32_t) ((p.n + kSwStep - 1) / kSwStep);
-#if MGPU_SW_DEAL
-#if MGPU_SW_STATIC_BLOCK > 0
-    constexpr uint32_t kStatB = MGPU_SW_STATIC_BLOCK;
-    const uint32_t n_static = (uint32_t) ((uint64_t) nsteps * MGPU_SW_STATIC_PCT / 100u / nwaves) / kStatB * kStatB;   // steps every wave takes without asking: whole blocks
-    const uint32_t nstat_blk = n_static / kStatB;
+    const uint32_t n_static = (uint32_t) ((uint64_t) nsteps * kSwStaticPct / 100u / nwaves) / kSwStaticBlock * kSwStaticBlock;   // steps every wave takes without asking: whole blocks
+    const uint32_t nstat_blk = n_static / kSwStaticBlock;
     uint32_t stat_blk = 0;
-    uint32_t st_next = wave_global * kStatB;
-    const uint32_t st_end = st_next + (n_static ? kStatB : 0u);
-#else
-    const uint32_t n_static = nsteps / nwaves / 2u;                                          // steps every wave takes without asking
-    uint32_t st_next = wave_global * n_static;
-    const uint32_t st_end = st_next + n_static;
-#endif
+    uint32_t st_next = wave_global * kSwStaticBlock;
+    const uint32_t st_end = st_next + (n_static ? kSwStaticBlock : 0u);
     // the dealt region [n_static * nwaves, nsteps) in blocks, the blocks in contiguous ranges per pool
     const uint32_t dyn_lo = n_static * nwaves;
     const uint32_t nblk = (nsteps - dyn_lo + kSwDealSteps - 1) / kSwDealSteps;
@@ -232,10 +196,6 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, SweepLds *s_w, 
     const uint32_t pool = blockIdx.x % npools;
     const uint32_t b_lo = (uint32_t) ((uint64_t) nblk * pool / npools), b_hi = (uint32_t) ((uint64_t) nblk * (pool + 1) / npools);
     uint32_t *const deal = p.dealer + (size_t) (kDealerCounters + pool) * kDealerStride;    // (k_slice's counters are the first kDealerCounters)
-#else
-    uint32_t st_next = (uint32_t) ((uint64_t) nsteps * wave_global / nwaves);
-    const uint32_t st_end = (uint32_t) ((uint64_t) nsteps * (wave_global + 1) / nwaves);
-#endif
 
     // Packed coefficients of the threshold tests, NEGATED (see the header comment): the accumulators hold
     // thr * base_noise - 32 * pa_mag - 32, negative <=> the phase reaches the threshold, so a sign bit is a phase bit.
@@ -258,7 +218,6 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, SweepLds *s_w, 
     uint32_t rng_next = st_next, rng_end = st_end;           // what is left of the range being swept: the wave's contiguous share first, then one dealt block after the other
     uint32_t next_blk = 0xffffffffu;                         // the block the pool's dealer has answered with (>= b_hi: the pool is empty)
     bool ask_now = false;                                    // a block was taken in this step: ask for the one after it (below)
-#if MGPU_SW_DEAL
     // A request goes out in the step that takes a block — and in the wave's first step — and its answer is read at the end of the same
     // step, a whole step later.  (A wave with fewer than two contiguous steps — a small chunk — waits for its first block at once: the
     // block's first step is prefetched while the step before it is swept, so it has to be known at the top of that one.)
@@ -271,18 +230,11 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, SweepLds *s_w, 
             next_blk = b_lo + rfl(t0);
         }
     }
-#endif
     // the next step of the wave's sequence, kNone = none left (a macro, not a lambda: with the by-reference captures of a lambda the
     // cursors ended up in scratch memory)
-#if MGPU_SW_DEAL
-#if MGPU_SW_STATIC_BLOCK > 0
-#define SW_STATIC_NEXT(dst) else if (++stat_blk < nstat_blk) { rng_next = (stat_blk * nwaves + wave_global) * kStatB; rng_end = rng_next + kStatB; dst = rng_next++; }
-#else
-#define SW_STATIC_NEXT(dst)
-#endif
 #define SW_ADVANCE(dst) do { \
         if (rng_next < rng_end) dst = rng_next++; \
-        SW_STATIC_NEXT(dst) \
+        else if (++stat_blk < nstat_blk) { rng_next = (stat_blk * nwaves + wave_global) * kSwStaticBlock; rng_end = rng_next + kSwStaticBlock; dst = rng_next++; } \
         else if (next_blk < b_hi) { \
             rng_next = dyn_lo + next_blk * kSwDealSteps; \
             rng_end = rng_next + kSwDealSteps < nsteps ? rng_next + kSwDealSteps : nsteps; \
@@ -291,9 +243,6 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, SweepLds *s_w, 
             dst = rng_next++; \
         } else dst = kNone; \
     } while (0)
-#else
-#define SW_ADVANCE(dst) do { if (rng_next < rng_end) dst = rng_next++; else dst = kNone; } while (0)
-#endif
     if constexpr (FUSED) {
         // the magnitudes behind the last scan position — the last 326 samples, which the last positions' look-ahead and the next
         // chunk's tail read — lie in steps nobody sweeps: one wave stages them, for their magnitudes and sums only
@@ -346,9 +295,6 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, SweepLds *s_w, 
     CvAcc run = {0, 0, 0, 0, 0};                             // FUSED: the byte sums of the run of contiguous steps being swept (sweep_flush_sums)
     uint32_t run_steps = 0;
     const uint32_t buf_shift = 31u - (uint32_t) __builtin_clz(p.buf_steps | 1u);   // (buf_steps: a power of two)
-#if MGPU_SW_TOUCH
-    uint32_t touch = 0;
-#endif
 
     // ---- threshold tests for up to 64 pre-check survivors, lane = survivor.  `s_cur` = the step being swept (its samples are
     //      in the half at hoff_cur); the queue is in the order the wave swept, so what is left of step s_prev comes first ----
@@ -359,13 +305,8 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, SweepLds *s_w, 
             const uint32_t *q = w32 + (idx1 >> 1);
             const uint32_t sh = (uint32_t) idx1 << 4;        // (v_alignbit uses the low five bits: 0 or 16)
             uint32_t d[10];
-#if MGPU_SW_EXP == 1
-#pragma unroll
-            for (int k = 0; k < 10; ++k) d[k] = (uint32_t) idx1 * (uint32_t) (k + 3) + (uint32_t) (uintptr_t) q;
-#else
 #pragma unroll
             for (int k = 0; k < 10; ++k) d[k] = q[k];
-#endif
 #define PAIR(k) __builtin_bit_cast(v2i16, __builtin_amdgcn_alignbit(d[(k) + 1], d[k], sh))   /* (pa[2k+1], pa[2k+2]), biased */
             const v2i16 P0 = PAIR(0), P1 = PAIR(1), P2 = PAIR(2), P3 = PAIR(3), P4 = PAIR(4), P5 = PAIR(5), P7 = PAIR(7), P8 = PAIR(8);
 #undef PAIR
@@ -384,9 +325,6 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, SweepLds *s_w, 
             x6 = __builtin_amdgcn_sdot2(P0, k6a, x5 + kBias6, false);
             x6 = __builtin_amdgcn_sdot2(P1, k6b, x6, false);
             x6 = __builtin_amdgcn_sdot2(P4, k6c, x6, false);
-#if MGPU_SW_EXP == 2
-            x4 = x5 = x6 = (int) ((d[0] ^ d[1] ^ d[2] ^ d[3] ^ d[4] ^ d[5] ^ d[6] ^ d[7] ^ d[8] ^ d[9]) & 0x7fffffffu);
-#endif
         }
         const int any = x4 | x5 | x6;                        // negative <=> a candidate
         const uint64_t cm = __ballot(any < 0);
@@ -399,8 +337,8 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, SweepLds *s_w, 
             // (selects of 0 / a scalar and three-operand adds: two instructions per value where a select between two scalars takes four)
             const int slot = rank + cnt_old + (is_cur ? dlist + cnt_cur - nold - cnt_old : 0);
             // position in the chunk = step * 1024 + sample index - the half's offset; the code carries it modulo the unit
-            const uint32_t pb_old = s_prev * (uint32_t) kSwStep - (uint32_t) (MGPU_SW_NBUF == 2 ? kSwHalf - hoff_cur : 0) - 1u;
-            const uint32_t pb_step = (uint32_t) dlist - (uint32_t) hoff_cur + (uint32_t) (MGPU_SW_NBUF == 2 ? kSwHalf - hoff_cur : 0);   // pb_cur - pb_old
+            const uint32_t pb_old = s_prev * (uint32_t) kSwStep - (uint32_t) (kSwHalf - hoff_cur) - 1u;
+            const uint32_t pb_step = (uint32_t) dlist - (uint32_t) hoff_cur + (uint32_t) (kSwHalf - hoff_cur);   // pb_cur - pb_old
             const uint32_t pos = (uint32_t) idx1 + pb_old + (is_cur ? pb_step : 0u);
             uint32_t code = (pos << 1) | ((uint32_t) x6 >> 31);                          // ... << 3 | phase mask: bit 2 = phase 8, bit 1 = phases 6/7, bit 0 = phases 4/5
             code = (code << 1) | ((uint32_t) x5 >> 31);
@@ -421,7 +359,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, SweepLds *s_w, 
     const unsigned long long pace_t0 = __builtin_amdgcn_s_memrealtime();
     int hoff = 0;                                            // this step's half of the tile: they alternate
     const uint32_t s_ragged = last_bits < (uint32_t) kSwStep ? nsteps - 1u : kNone;   // the step with positions beyond the end of the stream, if any
-    for (; cur != kNone; s_prev = cur, have_prev = true, cur = nxt, ++done, hoff = MGPU_SW_NBUF == 2 ? hoff ^ kSwHalf : 0) {
+    for (; cur != kNone; s_prev = cur, have_prev = true, cur = nxt, ++done, hoff ^= kSwHalf) {
         const uint32_t s = cur;
         if (pace) {
             const uint32_t t = (uint32_t) (__builtin_amdgcn_s_memrealtime() - pace_t0);
@@ -449,13 +387,8 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, SweepLds *s_w, 
                     mh = cv_lookup2(s_lut, preh);
                 }
                 uint16_t *out = p.mag_w + (uint64_t) s * kSwStep + 8 * lane;
-#if MGPU_SW_NT_STORE
-                __builtin_nontemporal_store(u32x4{a0, a1, a2, a3}, (u32x4 *) out);
-                __builtin_nontemporal_store(u32x4{b0, b1, b2, b3}, (u32x4 *) (out + 512));
-#else
                 *(u32x4 *) out = u32x4{a0, a1, a2, a3};
                 *(u32x4 *) (out + 512) = u32x4{b0, b1, b2, b3};
-#endif
                 *(u32x4 *) &L.mag[hoff + 8 * lane] = u32x4{a0 ^ 0x80008000u, a1 ^ 0x80008000u, a2 ^ 0x80008000u, a3 ^ 0x80008000u};
                 *(u32x4 *) &L.mag[hoff + 512 + 8 * lane] = u32x4{b0 ^ 0x80008000u, b1 ^ 0x80008000u, b2 ^ 0x80008000u, b3 ^ 0x80008000u};
                 if (lane < 16) *(uint32_t *) &L.mag[hoff + kSwStep + 2 * lane] = mh ^ 0x80008000u;
@@ -487,29 +420,19 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, SweepLds *s_w, 
         if constexpr (FUSED) {                               // the run ends where the wave's sequence jumps (or ends)
             if (run_steps && (nxt != s + 1u || run_steps >= kSwRunMax)) { sweep_flush_sums(run, p.sum_level, p.sum_power, s >> buf_shift); run_steps = 0; }
         }
-#if MGPU_SW_DEAL
         const bool asked_now = ask_now;                      // (also a block taken before the loop, by the wave's very first step)
         ask_now = false;
 #define SW_ANSWER() do { if (asked_now) next_blk = b_lo + rfl(ticket); } while (0)   /* the step's last act (wave-uniform; the request is a step old) */
-#else
-#define SW_ANSWER() do { } while (0)
-#endif
         if constexpr (FUSED) {
             if (nxt != kNone && !careful(nxt)) fetch_iq(nxt);
         } else if (nxt != kNone) {
             src = p.mag + (uint64_t) nxt * kSwStep + 8 * lane;
             pre0 = *(const u32x4 *) src; pre1 = *(const u32x4 *) (src + 512); pre2 = *(const u32x4 *) (src + halo_off);
         }
-#if MGPU_SW_DEAL
         // the request for the block after the one just taken: BEHIND the loads (the compiler's waits for them are counted from the
         // youngest operation: a request ahead of them would be waited for with them), into a variable of this iteration (deal_ask)
         uint32_t ticket;
         if (asked_now && lane == 0) ticket = deal_ask(deal, deal_zero);
-#endif
-#if MGPU_SW_TOUCH
-        asm volatile("" : : "v"(touch));                     // (the touch issued a step ago: long since there)
-        if (nxt != kNone && rng_next < rng_end) touch = *(const uint32_t *) (src + kSwStep + 8 * lane);   // the step behind nxt, where it is the wave's too
-#endif
         WAVE_SYNC();
 #if MGPU_SW_STAGE == 1
         dbg_sink += w32[lane];
@@ -603,7 +526,6 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, SweepLds *s_w, 
         // The other half is staged next: whatever of the step before this one is still waiting goes first.  One full round
         // takes all of it (fewer than 64 were left); without one, a short round of exactly those.
         if (!ran && rem_old) eval_round(rem_old, s, hoff);
-        if (MGPU_SW_NBUF == 1 && pqn > pqh) eval_round(pqn - pqh, s, hoff);   // (one half: nothing may wait across the next staging)
         // the previous step's list is complete
         if (have_prev) p.cand_count[s_prev] = (uint32_t) cnt_old;            // (every lane stores the same word)
         cnt_old = cnt_cur; cnt_cur = 0;
@@ -629,7 +551,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, SweepLds *s_w, 
 }
 
 // the sweep over a magnitude array (struct mag_buf entry, SC16 formats, Mode A/C; tools/micro/sweep_cold.hip): the roofline's kernel
-__global__ __launch_bounds__(kBlock, MGPU_SW_NBUF == 2 ? 6 : 8) void k_sweep(SweepParams p) {
+__global__ __launch_bounds__(kBlock, 6) void k_sweep(SweepParams p) {
     __shared__ __attribute__((aligned(16))) SweepLds s_w[kBlock / WAVE];
     sweep_body<kBlock, kSwPlain>(p, s_w, nullptr);
 }

@@ -134,7 +134,7 @@ int main(int argc, char **argv) {
             float us;
             if (run(r, us)) return 2;
             if (rd > 0) cold.push_back(us);                // (the first round also pays the first-touch of the code and the TLBs)
-            if (rd == 0 && MGPU_SW_STAGE == 0 && MGPU_SW_EXP != 1 && MGPU_SW_EXP != 2 && (r == 0 || r == replicas - 1)) {
+            if (rd == 0 && MGPU_SW_STAGE == 0 && (r == 0 || r == replicas - 1)) {
                 CK(hipMemcpy(hc.data(), d_cand, hc.size() * 2, hipMemcpyDeviceToHost));
                 CK(hipMemcpy(hn.data(), d_count, (size_t) (nsteps + 1) * 4, hipMemcpyDeviceToHost));
                 std::vector<uint32_t> got;
@@ -179,14 +179,14 @@ int main(int argc, char **argv) {
     stat(cold, cmin, cmed, cmax, cavg);
     stat(warm, wmin, wmed, wmax, wavg);
     const double bytes = (double) n * 2.0;
-    printf("{\"kernel\": \"k_sweep\", \"variant\": \"exp %d nbuf %d deal %d touch %d\", \"stage\": %d, \"samples_per_launch\": %llu, \"algorithmic_bytes_per_launch\": %.0f, \"replicas\": %d, "
+    printf("{\"kernel\": \"k_sweep\", \"stage\": %d, \"samples_per_launch\": %llu, \"algorithmic_bytes_per_launch\": %.0f, \"replicas\": %d, "
            "\"cold_array_bytes\": %.0f, \"pace_ticks\": %.0f, \"blocks\": %u, \"waves\": %u, \"dense\": %d, \"rate\": %.0f, \"candidates\": %llu, \"candidates_cpu\": %zu, "
            "\"mismatches_vs_cpu_scan\": %llu, "
            "\"cold_us\": {\"min\": %.2f, \"median\": %.2f, \"mean\": %.2f, \"max\": %.2f, \"launches\": %zu}, "
            "\"cold_GBs\": %.1f, \"cold_frac_of_8TBs\": %.4f, "
            "\"warm_us\": {\"min\": %.2f, \"median\": %.2f, \"mean\": %.2f, \"max\": %.2f, \"launches\": %zu}, \"warm_GBs\": %.1f, \"warm_frac_of_8TBs\": %.4f, "
            "\"waves_alive_frac\": %.3f, \"wave_life_mean_us\": %.2f, \"last_start_us\": %.2f, \"end_us\": {\"p10\": %.2f, \"p50\": %.2f, \"p90\": %.2f, \"max\": %.2f}}\n",
-           (int) MGPU_SW_EXP, (int) MGPU_SW_NBUF, (int) MGPU_SW_DEAL, (int) MGPU_SW_TOUCH, (int) MGPU_SW_STAGE, (unsigned long long) n, bytes, replicas, (double) replicas * stride * 2, (double) pace_ticks, blocks, nwaves, dense, rate,
+           (int) MGPU_SW_STAGE, (unsigned long long) n, bytes, replicas, (double) replicas * stride * 2, (double) pace_ticks, blocks, nwaves, dense, rate,
            (unsigned long long) ncand, want.size(), (unsigned long long) mismatches,
            cmin, cmed, cavg, cmax, cold.size(), bytes / (cavg * 1e-6) / 1e9, bytes / (cavg * 1e-6) / 1e9 / 8000.0,
            wmin, wmed, wavg, wmax, warm.size(), bytes / (wavg * 1e-6) / 1e9, bytes / (wavg * 1e-6) / 1e9 / 8000.0,
