@@ -592,7 +592,7 @@ int mgpu_decode_fields_device(mgpu_ctx *ctx, const struct mgpu_msg *d_msgs, uint
  * hands it (net_io.c:5924-5940: one sample buffer's messages, cut every 256, all updates before all outputs):
  *     forwarded  <=>  (crc == 0 && correctedbits == 0)  ||  (mm->aircraft && mm->aircraft->messages > 1)  ||  Mode A/C
  * (the beast and raw outputs additionally want correctedbits < 2, net_io.c:5863-5872: the caller's test, it needs nothing from here).
- * The position tracker itself (cpr.c, the speed / range checks, track.c:423-745) stays on the host: when it judges a position
+ * The position tracker's checks (the speed / range checks, track.c:423-745; cpr.c itself: mgpu_cpr_track below) stay on the host: when it judges a position
  * message bad or duplicate it puts the aircraft's copy back, a->messages and a->seen with it (track.c:2625-2627), and it deletes
  * aircraft without a reliable position after 5 silent minutes (track.c:2856-2880).  The gate carries both as BOUNDS per aircraft
  * and answers "deferred" exactly where the bounds disagree — in practice inside an aircraft's first two messages only: 0.2 % of a
@@ -643,6 +643,78 @@ int mgpu_beast_encode_gated(mgpu_ctx *ctx, const struct mgpu_msg *msgs, uint64_t
 int mgpu_beast_encode_gated_device(mgpu_ctx *ctx, const struct mgpu_msg *d_msgs, const uint8_t *d_verdict, uint64_t n, uint32_t flags,
                                    uint8_t *d_out, uint64_t cap, uint64_t *bytes, struct mgpu_deferred *d_deferred, uint64_t deferred_cap,
                                    uint64_t *ndeferred);
+
+/* ---- position decode: CPR pairing and cpr.c over the message list (kernels/cpr.inc) ---------------------------------------------
+ * What updatePosition does with a position message before its plausibility checks, on the device, one record per message (same
+ * index).  Per position message (MGPU_F_CPR_VALID, DF17 / DF18), in stream order per address (fields.addr & 0x1ffffff):
+ *   1. the aircraft's even or odd slot becomes this message's {cpr_lat, cpr_lon, cpr_type, source, sysTimestamp} (accept_cpr,
+ *      track.c:1829-1844);
+ *   2. max_elapsed = surface (cpr_type == CPR_SURFACE): 50 000 ms if MGPU_F_GS_VALID && gs_selected <= 25, else 25 000
+ *      (track.c:1266-1269); airborne: cfg.airborne_max_elapsed_ms, 0 = 10 000, the reference's fallback (track.c:1237);
+ *   3. GLOBAL decode (doGlobalCPR's decode, track.c:758-799: decodeCPRsurface / decodeCPRairborne, cpr.c:170-319) iff both slots are
+ *      filled, of the same cpr_type and source, and |t_even - t_odd| <= max_elapsed (track.c:1279-1282); fflag = this message is odd;
+ *      surface needs cfg.ref_valid (the user location, track.c:763-766), result -1 without it.  0: method GLOBAL; -2: method BAD, no
+ *      position; -1 or not attempted: 4;
+ *   4. LOCAL decode (doLocalCPR's decode, track.c:862-914: decodeCPRrelative, cpr.c:331-374) relative to the aircraft's last GLOBAL
+ *      result of this stage if one exists and now < its time + 10 min (method LOCAL_AIRCRAFT), else if airborne && cfg.ref_valid relative
+ *      to the receiver (LOCAL_RECEIVER), else none; a result < 0 gives method NONE.
+ * Every other message (Mode A/C, no position, MGPU_F_CPR_VALID clear) gets an all-zero record and touches no state.
+ * Differences from the reference, by design — the host's tracker keeps the plausibility checks (speed_check, the greatcircle range
+ * limits, accept_data, duplicates: track.c:423-745, 784-792, 813-838, 919-956) and receives a candidate position per message instead
+ * of two integers:
+ *   - the speed-dependent airborne window (track.c:1239-1246) reads the tracker's a->gs: not here, set airborne_max_elapsed_ms;
+ *   - the reference's local decode refers to the tracker's latest ACCEPTED position (a->lat / a->lon, track.c:862-864), which a local
+ *     result may have moved; here only GLOBAL results of this stage move the per-aircraft reference;
+ *   - the slots never expire on their own (the reference invalidates stale ones elsewhere); the window of rule 3 bounds their age.
+ * The arithmetic is the reference's in IEEE double, operation for operation: lat / lon equal cpr.c's bit for bit.
+ * The aircraft table (device memory, 2^25 addresses x 64 bytes = 2 GiB, allocated by the first call) lives from call to call until
+ * mgpu_cpr_reset / mgpu_destroy: one list cut into several calls gives the same records as one call (but for `partner`, which
+ * counts in the call's own list).  Preconditions as for mgpu_track_gate: netUseMessage order, n < 2^32 - 2.  n == 0 is MGPU_OK; a NULL
+ * cfg or a non-finite reference location is MGPU_E_INVAL.  The entries run on the stream the gate and the encoder use: they do not
+ * wait for queued feeds. */
+struct mgpu_cpr_config {
+    double   ref_lat, ref_lon;    /* Modes.fUserLat / fUserLon */
+    uint32_t ref_valid;           /* Modes.userLocationValid */
+    uint32_t airborne_max_elapsed_ms;   /* 0 = 10 000 */
+};
+#define MGPU_CPR_NONE            0
+#define MGPU_CPR_GLOBAL          1
+#define MGPU_CPR_LOCAL_RECEIVER  2
+#define MGPU_CPR_LOCAL_AIRCRAFT  3
+#define MGPU_CPR_BAD             4
+#define MGPU_CPR_NOT_TRIED       1            /* global_result / local_result: that decode was not attempted */
+#define MGPU_CPR_PARTNER_NONE    0xffffffffu  /* no global decode attempted */
+#define MGPU_CPR_PARTNER_EARLIER 0xfffffffeu  /* the other half arrived in an earlier call */
+struct mgpu_position {            /* 32 bytes, one per message, same index */
+    double   lat, lon;            /* set for GLOBAL / LOCAL_*; 0 otherwise */
+    uint32_t partner;             /* index in THIS call's list of the opposite-parity message the global decode used, or MGPU_CPR_PARTNER_* */
+    int32_t  partner_dt_ms;       /* this message's sysTimestamp - the partner's (0 without one) */
+    int8_t   global_result, local_result;   /* cpr.c's 0 / -1 / -2; MGPU_CPR_NOT_TRIED */
+    uint8_t  method;              /* MGPU_CPR_NONE / _GLOBAL / _LOCAL_RECEIVER / _LOCAL_AIRCRAFT / _BAD */
+    uint8_t  flags;               /* bit 0 odd, bit 1 surface */
+    uint8_t  reserved[4];
+};
+int mgpu_cpr_track(mgpu_ctx *ctx, const struct mgpu_cpr_config *cfg, const struct mgpu_msg *msgs, uint64_t n, struct mgpu_position *out);   /* host arrays; decodes the fields itself, like mgpu_track_gate */
+int mgpu_cpr_track_device(mgpu_ctx *ctx, const struct mgpu_cpr_config *cfg, const struct mgpu_msg *d_msgs, const struct mgpu_fields *d_fields,
+                          uint64_t n, struct mgpu_position *d_out);   /* everything in device memory */
+int mgpu_cpr_reset(mgpu_ctx *ctx);
+
+/* cpr.c's decoders alone, one case per record (stateless): decodeCPRairborne (cpr.c:170-221), decodeCPRsurface (:223-319),
+ * decodeCPRrelative (:331-374) with cprNLFunction (:79-146) behind them. */
+struct mgpu_cpr_case {
+    double   reflat, reflon;      /* fn 1, 2 */
+    int32_t  even_lat, even_lon, odd_lat, odd_lon;   /* fn 2: the message's words in even_* */
+    uint8_t  fn;                  /* 0 airborne, 1 surface, 2 relative */
+    uint8_t  fflag, surface;      /* surface: fn 2 only */
+    uint8_t  pad[5];
+};
+struct mgpu_cpr_result {
+    double   lat, lon;            /* rc < 0: 0 */
+    int32_t  rc;                  /* 0 / -1 / -2 as cpr.c returns them */
+    int32_t  pad;
+};
+int mgpu_cpr_decode(mgpu_ctx *ctx, const struct mgpu_cpr_case *cases, uint64_t n, struct mgpu_cpr_result *out);
+int mgpu_cpr_decode_device(mgpu_ctx *ctx, const struct mgpu_cpr_case *d_cases, uint64_t n, struct mgpu_cpr_result *d_out);
 
 /* ---- tables, for known-answer tests against crc.c --------------------------------- */
 

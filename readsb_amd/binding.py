@@ -47,6 +47,28 @@ FIELDS_DTYPE = np.dtype([
 assert FIELDS_DTYPE.itemsize == 176
 
 
+# struct mgpu_position, mgpu_cpr_case, mgpu_cpr_result (include/modes_gpu.h): CPR pairing and position decode
+POSITION_DTYPE = np.dtype([
+    ("lat", "<f8"), ("lon", "<f8"), ("partner", "<u4"), ("partner_dt_ms", "<i4"), ("global_result", "i1"), ("local_result", "i1"),
+    ("method", "u1"), ("flags", "u1"), ("reserved", "u1", 4),
+])
+assert POSITION_DTYPE.itemsize == 32
+CPR_CASE_DTYPE = np.dtype([
+    ("reflat", "<f8"), ("reflon", "<f8"), ("even_lat", "<i4"), ("even_lon", "<i4"), ("odd_lat", "<i4"), ("odd_lon", "<i4"),
+    ("fn", "u1"), ("fflag", "u1"), ("surface", "u1"), ("pad", "u1", 5),
+])
+assert CPR_CASE_DTYPE.itemsize == 40
+CPR_RESULT_DTYPE = np.dtype([("lat", "<f8"), ("lon", "<f8"), ("rc", "<i4"), ("pad", "<i4")])
+assert CPR_RESULT_DTYPE.itemsize == 24
+CPR_NONE, CPR_GLOBAL, CPR_LOCAL_RECEIVER, CPR_LOCAL_AIRCRAFT, CPR_BAD = 0, 1, 2, 3, 4
+CPR_NOT_TRIED = 1
+CPR_PARTNER_NONE, CPR_PARTNER_EARLIER = 0xFFFFFFFF, 0xFFFFFFFE
+
+
+class CprConfig(C.Structure):                                         # struct mgpu_cpr_config
+    _fields_ = [("ref_lat", C.c_double), ("ref_lon", C.c_double), ("ref_valid", C.c_uint32), ("airborne_max_elapsed_ms", C.c_uint32)]
+
+
 FILTER_CLOCK_AFTER_FIRST, FILTER_CLOCK_BEFORE_FIRST, FILTER_CLOCK_EXTERNAL = 0, 1, 2
 
 
@@ -285,6 +307,11 @@ def load_library():
     lib.mgpu_track_gate.argtypes = [vp, vp, u64, vp]
     lib.mgpu_track_gate_device.argtypes = [vp, vp, vp, u64, vp]
     lib.mgpu_track_gate_reset.argtypes = [vp]
+    lib.mgpu_cpr_track.argtypes = [vp, C.POINTER(CprConfig), vp, u64, vp]
+    lib.mgpu_cpr_track_device.argtypes = [vp, C.POINTER(CprConfig), vp, vp, u64, vp]
+    lib.mgpu_cpr_reset.argtypes = [vp]
+    lib.mgpu_cpr_decode.argtypes = [vp, vp, u64, vp]
+    lib.mgpu_cpr_decode_device.argtypes = [vp, vp, u64, vp]
     lib.mgpu_beast_encode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
     lib.mgpu_beast_encode_gated.argtypes = [vp, vp, u64, u32, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64)]
     lib.mgpu_beast_encode_gated_device.argtypes = [vp, vp, vp, u64, u32, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64)]
@@ -578,6 +605,42 @@ class Demodulator:
 
     def track_gate_reset(self):
         self._chk(self.lib.mgpu_track_gate_reset(self.ctx), "mgpu_track_gate_reset")
+
+    @staticmethod
+    def _cpr_config(ref, airborne_max_elapsed_ms):
+        cfg = CprConfig(0.0, 0.0, 0, int(airborne_max_elapsed_ms))
+        if ref is not None:
+            cfg.ref_lat, cfg.ref_lon, cfg.ref_valid = float(ref[0]), float(ref[1]), 1
+        return cfg
+
+    def cpr_track(self, msgs, ref=None, airborne_max_elapsed_ms=0):
+        """CPR pairing and position decode on the GPU (include/modes_gpu.h, mgpu_cpr_track): one POSITION_DTYPE record per message.
+        ref: the receiver's (lat, lon) or None; the aircraft table lives on the device from call to call (cpr_reset)."""
+        msgs = np.ascontiguousarray(msgs)
+        assert msgs.dtype == MSG_DTYPE
+        out = np.empty(len(msgs), dtype=POSITION_DTYPE)
+        cfg = self._cpr_config(ref, airborne_max_elapsed_ms)
+        self._chk(self.lib.mgpu_cpr_track(self.ctx, C.byref(cfg), C.c_void_p(msgs.ctypes.data), len(msgs), C.c_void_p(out.ctypes.data)), "mgpu_cpr_track")
+        return out
+
+    def cpr_track_device(self, d_msgs_ptr, d_fields_ptr, n, d_out_ptr, ref=None, airborne_max_elapsed_ms=0):
+        cfg = self._cpr_config(ref, airborne_max_elapsed_ms)
+        self._chk(self.lib.mgpu_cpr_track_device(self.ctx, C.byref(cfg), C.c_void_p(d_msgs_ptr), C.c_void_p(d_fields_ptr), n, C.c_void_p(d_out_ptr)),
+                  "mgpu_cpr_track_device")
+
+    def cpr_reset(self):
+        self._chk(self.lib.mgpu_cpr_reset(self.ctx), "mgpu_cpr_reset")
+
+    def cpr_decode(self, cases):
+        """cpr.c's decoders on the GPU, one CPR_CASE_DTYPE record per case -> CPR_RESULT_DTYPE records."""
+        cases = np.ascontiguousarray(cases)
+        assert cases.dtype == CPR_CASE_DTYPE
+        out = np.empty(len(cases), dtype=CPR_RESULT_DTYPE)
+        self._chk(self.lib.mgpu_cpr_decode(self.ctx, C.c_void_p(cases.ctypes.data), len(cases), C.c_void_p(out.ctypes.data)), "mgpu_cpr_decode")
+        return out
+
+    def cpr_decode_device(self, d_cases_ptr, n, d_out_ptr):
+        self._chk(self.lib.mgpu_cpr_decode_device(self.ctx, C.c_void_p(d_cases_ptr), n, C.c_void_p(d_out_ptr)), "mgpu_cpr_decode_device")
 
     def beast_encode(self, msgs):
         """Beast wire stream (bytes) of a record array (host memory in, host memory out, encoded on the GPU)."""

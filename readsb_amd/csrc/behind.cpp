@@ -1,5 +1,7 @@
-// behind.cpp — behind the message list: beast encoder, field decode, tracking gate, and the CRC / table diagnostics.
+// behind.cpp — behind the message list: beast encoder, field decode, tracking gate, position decode, and the CRC / table diagnostics.
 #include "ctx.h"
+
+#include <cmath>
 
 extern "C" {
 
@@ -219,6 +221,95 @@ int mgpu_beast_encode_gated(mgpu_ctx *c, const struct mgpu_msg *msgs, uint64_t n
     if (rc != MGPU_OK) return rc;
     HIPCHK(c, hipMemcpy(out, c->d_beast_out, *bytes, hipMemcpyDeviceToHost));
     if (*ndeferred) HIPCHK(c, hipMemcpy(deferred, c->d_deferred, *ndeferred * sizeof(mgpu_deferred), hipMemcpyDeviceToHost));
+    return MGPU_OK;
+}
+
+// ---- CPR pairing + position decode (track.c:1249-1282, 1827-1850, 758-799, 862-914; cpr.c:62-374), kernels/cpr.inc ----
+
+static int cpr_reserve(mgpu_ctx *c, uint64_t n) {
+    if (!c->d_cpr_table) {
+        HIPCHK(c, hipMalloc(&c->d_cpr_table, cpr_table_bytes()));
+        HIPCHK(c, hipMemsetAsync(c->d_cpr_table, 0, cpr_table_bytes(), c->stream_aux));
+    }
+    if (n > c->cpr_cap) {
+        if (c->d_cpr_scratch) (void) hipFree(c->d_cpr_scratch);
+        if (c->d_cpr_out) (void) hipFree(c->d_cpr_out);
+        c->d_cpr_scratch = nullptr; c->d_cpr_out = nullptr; c->cpr_cap = 0;
+        const uint64_t want = n + n / 4 + 1024;
+        HIPCHK(c, hipMalloc(&c->d_cpr_scratch, cpr_scratch_bytes(want)));
+        HIPCHK(c, hipMalloc(&c->d_cpr_out, want * sizeof(mgpu_position)));
+        c->cpr_cap = want;
+    }
+    return MGPU_OK;
+}
+
+static bool cpr_config_ok(const struct mgpu_cpr_config *cfg) { return cfg && std::isfinite(cfg->ref_lat) && std::isfinite(cfg->ref_lon); }
+
+int mgpu_cpr_reset(mgpu_ctx *c) {
+    if (!c) return MGPU_E_INVAL;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (c->d_cpr_table) {
+        HIPCHK(c, hipMemsetAsync(c->d_cpr_table, 0, cpr_table_bytes(), c->stream_aux));
+        HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    }
+    return MGPU_OK;
+}
+
+int mgpu_cpr_track_device(mgpu_ctx *c, const struct mgpu_cpr_config *cfg, const struct mgpu_msg *d_msgs, const struct mgpu_fields *d_fields, uint64_t n,
+                          struct mgpu_position *d_out) {
+    if (!c || !cpr_config_ok(cfg) || (n && (!d_msgs || !d_fields || !d_out)) || n >= 0xfffffffeull) return MGPU_E_INVAL;
+    if (n == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (int rc = cpr_reserve(c, n)) return rc;
+    launch_cpr_track(d_msgs, d_fields, n, *cfg, c->d_cpr_table, c->d_cpr_scratch, d_out, c->stream_aux);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    return MGPU_OK;
+}
+
+int mgpu_cpr_track(mgpu_ctx *c, const struct mgpu_cpr_config *cfg, const struct mgpu_msg *msgs, uint64_t n, struct mgpu_position *out) {
+    if (!c || !cpr_config_ok(cfg) || (n && (!msgs || !out)) || n >= 0xfffffffeull) return MGPU_E_INVAL;
+    if (n == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (int rc = fields_reserve(c, n)) return rc;
+    if (int rc = cpr_reserve(c, n)) return rc;
+    if (int rc = stage_messages(c, msgs, n)) return rc;
+    launch_decode_fields((const mgpu_msg *) c->d_beast_in, n, c->d_fields, c->d_roll_tan, c->stream_aux);
+    launch_cpr_track((const mgpu_msg *) c->d_beast_in, c->d_fields, n, *cfg, c->d_cpr_table, c->d_cpr_scratch, (mgpu_position *) c->d_cpr_out, c->stream_aux);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, c->d_cpr_out, n * sizeof(mgpu_position), hipMemcpyDeviceToHost, c->stream_aux));
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    return MGPU_OK;
+}
+
+int mgpu_cpr_decode_device(mgpu_ctx *c, const struct mgpu_cpr_case *d_cases, uint64_t n, struct mgpu_cpr_result *d_out) {
+    if (!c || (n && (!d_cases || !d_out))) return MGPU_E_INVAL;
+    if (n == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    launch_cpr_cases(d_cases, n, d_out, c->stream_aux);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    return MGPU_OK;
+}
+
+int mgpu_cpr_decode(mgpu_ctx *c, const struct mgpu_cpr_case *cases, uint64_t n, struct mgpu_cpr_result *out) {
+    if (!c || (n && (!cases || !out))) return MGPU_E_INVAL;
+    if (n == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (n > c->cpr_cases_cap) {                                  // cases, and their results behind them
+        if (c->d_cpr_cases) (void) hipFree(c->d_cpr_cases);
+        c->d_cpr_cases = nullptr; c->cpr_cases_cap = 0;
+        const uint64_t want = n + n / 4 + 1024;
+        HIPCHK(c, hipMalloc(&c->d_cpr_cases, want * (sizeof(mgpu_cpr_case) + sizeof(mgpu_cpr_result))));
+        c->cpr_cases_cap = want;
+    }
+    mgpu_cpr_case *d_cases = (mgpu_cpr_case *) c->d_cpr_cases;
+    mgpu_cpr_result *d_out = (mgpu_cpr_result *) (d_cases + c->cpr_cases_cap);
+    HIPCHK(c, hipMemcpyAsync(d_cases, cases, n * sizeof(mgpu_cpr_case), hipMemcpyHostToDevice, c->stream_aux));
+    launch_cpr_cases(d_cases, n, d_out, c->stream_aux);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, d_out, n * sizeof(mgpu_cpr_result), hipMemcpyDeviceToHost, c->stream_aux));
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
     return MGPU_OK;
 }
 

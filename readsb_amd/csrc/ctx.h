@@ -421,6 +421,10 @@ struct mgpu_ctx {
     void *d_gate_table = nullptr, *d_gate_scratch = nullptr;
     uint8_t *d_gate_verdict = nullptr;
     uint64_t gate_cap = 0;
+    // CPR pairing + position decode (kernels/cpr.inc): the aircraft table (2 GiB, allocated and zeroed by the first call), its scratch,
+    // the staged results / cases of the host-array entries
+    void *d_cpr_table = nullptr, *d_cpr_scratch = nullptr, *d_cpr_out = nullptr, *d_cpr_cases = nullptr;
+    uint64_t cpr_cap = 0, cpr_cases_cap = 0;
     uint32_t *d_beast_blocks = nullptr;
     mgpu_deferred *d_deferred = nullptr;                      // mgpu_beast_encode_gated's list, device side
     uint64_t deferred_cap = 0;

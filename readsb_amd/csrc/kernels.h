@@ -68,6 +68,7 @@ struct PhaseRec {
 };
 static_assert(sizeof(PhaseRec) == 32, "PhaseRec must be 32 bytes");
 static_assert(sizeof(mgpu_msg) == 64 && sizeof(mgpu_fields) == 176, "C-ABI record sizes");
+static_assert(sizeof(mgpu_position) == 32 && sizeof(mgpu_cpr_case) == 40 && sizeof(mgpu_cpr_result) == 24 && sizeof(mgpu_cpr_config) == 24, "C-ABI record sizes");
 
 // counters produced on the device (indices into a u64 array)
 enum {
@@ -211,6 +212,13 @@ size_t gate_table_bytes();
 size_t gate_scratch_bytes(uint64_t n);
 void launch_track_gate(const mgpu_msg *msgs, const mgpu_fields *fields, uint64_t n, uint32_t buf_samples, void *table, void *scratch,
                        uint8_t *verdict, hipStream_t s);
+// CPR pairing + position decode over a message list in device memory (kernels/cpr.inc): table = cpr_table_bytes() bytes, zeroed once and
+// kept from call to call; scratch = cpr_scratch_bytes(n); out: one record per message.  launch_cpr_cases: cpr.c's decoders, lane = case
+size_t cpr_table_bytes();
+size_t cpr_scratch_bytes(uint64_t n);
+void launch_cpr_track(const mgpu_msg *msgs, const mgpu_fields *fields, uint64_t n, const mgpu_cpr_config &cfg, void *table, void *scratch,
+                      mgpu_position *out, hipStream_t s);
+void launch_cpr_cases(const mgpu_cpr_case *cases, uint64_t n, mgpu_cpr_result *out, hipStream_t s);
 // signal power of accepted messages: sum of mag^2 over d_mag[pos+19 .. pos+19+len)
 void launch_signal_power(const uint16_t *mag, const uint32_t *pos, const uint16_t *len, uint32_t nmsg,
                          unsigned long long *out, hipStream_t s);

@@ -1,6 +1,8 @@
-"""Throughput of the two kernels behind the message list — k_decode_fields and k_beast_size/k_beast_write — on records
-resident in HBM (python tools/bench_behind.py [--messages N]).  Prints one JSON line per kernel: messages/s, algorithmic
-GB/s (64 + 176 B per message for the field decode; 64 B in + the frame bytes out for the encoder) against the
+"""Throughput of the stages behind the message list — k_decode_fields, k_beast_size/k_beast_write, the tracking gate
+(mgpu_track_gate_device) and the position decode (mgpu_cpr_track_device) — on records resident in HBM
+(python tools/bench_behind.py [--messages N]).  Prints one JSON line per stage: messages/s, algorithmic
+GB/s (64 + 176 B per message for the field decode; 64 B in + the frame bytes out for the encoder; for the gate and the
+position decode the records read and written once, 64 + 176 + 1 and 64 + 176 + 32 B, their sort's traffic not counted) against the
 8 TB/s HBM peak.  Wall clock around the C-ABI `_device` calls (launch + stream sync included), so run it under
 `rocprofv3 --kernel-trace --stats` for the kernels' own durations (profiles/r01_behind_*)."""
 import argparse
@@ -37,7 +39,8 @@ def main():
     hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
     hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     d = readsb_amd.Demodulator(max_samples=1 << 20)
-    d_in, d_f, d_b = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    d_in, d_f, d_b, d_v, d_p = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    assert hip.hipMalloc(C.byref(d_v), n) == 0 and hip.hipMalloc(C.byref(d_p), n * readsb_amd.binding.POSITION_DTYPE.itemsize) == 0
     assert hip.hipMalloc(C.byref(d_in), n * 64) == 0 and hip.hipMalloc(C.byref(d_f), n * readsb_amd.FIELDS_DTYPE.itemsize) == 0 and hip.hipMalloc(C.byref(d_b), n * 44) == 0
     for k in range(reps_in):
         assert hip.hipMemcpy(C.c_void_p(d_in.value + k * m.nbytes), m.ctypes.data, m.nbytes, 1) == 0
@@ -52,7 +55,26 @@ def main():
     for _ in range(a.reps):
         d.beast_encode_device(d_in.value, n, d_b.value, n * 44)
     t_b = (time.perf_counter() - t0) / a.reps
-    for name, t, algo in (("k_decode_fields", t_f, n * (64 + readsb_amd.FIELDS_DTYPE.itemsize)), ("k_beast_size+k_beast_write", t_b, n * 64 + nbytes)):
+    # the stages with a table: the same list every time (its aircraft are known from the second call on), the receiver's location set
+    ref = (52.0, 4.5)
+    for _ in range(2):
+        d.track_gate_device(d_in.value, d_f.value, n, d_v.value)
+        d.cpr_track_device(d_in.value, d_f.value, n, d_p.value, ref=ref)
+    t0 = time.perf_counter()
+    for _ in range(a.reps):
+        d.track_gate_device(d_in.value, d_f.value, n, d_v.value)
+    t_g = (time.perf_counter() - t0) / a.reps
+    t0 = time.perf_counter()
+    for _ in range(a.reps):
+        d.cpr_track_device(d_in.value, d_f.value, n, d_p.value, ref=ref)
+    t_c = (time.perf_counter() - t0) / a.reps
+    pos = np.empty(len(m), dtype=readsb_amd.binding.POSITION_DTYPE)
+    assert hip.hipMemcpy(pos.ctypes.data, d_p, pos.nbytes, 2) == 0
+    print(json.dumps({"list": "fuzzed frames", "position_messages_share": round(float(((pos["global_result"] != 0) | (pos["method"] != 0)).mean()), 4),
+                      "methods_in_first_block": {str(k): int((pos["method"] == k).sum()) for k in range(5)}}))
+    fb = readsb_amd.FIELDS_DTYPE.itemsize
+    for name, t, algo in (("k_decode_fields", t_f, n * (64 + fb)), ("k_beast_size+k_beast_write", t_b, n * 64 + nbytes),
+                          ("mgpu_track_gate_device", t_g, n * (64 + fb + 1)), ("mgpu_cpr_track_device", t_c, n * (64 + fb + 32))):
         print(json.dumps({"kernel": name, "messages": n, "ms": round(t * 1e3, 4), "messages_per_s": round(n / t),
                           "algorithmic_GBps": round(algo / t / 1e9, 1), "frac_of_hbm_peak": round(algo / t / 8e12, 4),
                           "timing": "wall clock around the C-ABI call, launch + sync included"}))
