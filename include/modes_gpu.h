@@ -461,7 +461,8 @@ double mgpu_seqsum_apply(double start, const struct mgpu_msg *msgs, uint64_t n, 
 /* ---- beast wire output (modesSendBeastOutput, net_io.c:1655-1714) ------------------------------------
  * Per message: 0x1a, type '2' (56-bit) / '3' (112-bit) / '1' (Mode A/C), the 12 MHz timestamp as 6 bytes
  * big-endian, one signal byte clamp(nearbyint(sqrt(signalLevel) * 255), 1..255), the (corrected) message
- * bytes; every 0x1a payload byte doubled; no 0x1a 0xe3 receiverId prefix.  Encoded on the GPU.
+ * bytes; every 0x1a payload byte doubled.  Encoded on the GPU.  These two entries write no 0x1a 0xe3 receiverId prefix and
+ * the corrected bytes; mgpu_beast_encode_ex* below adds --net-receiver-id and --net-verbatim.
  * _device: d_msgs / d_out are device pointers (e.g. the records an aggregator gathered into its HBM);
  * *bytes = size of the stream; MGPU_E_OVERFLOW (with *bytes set) if it does not fit cap. */
 int mgpu_beast_encode_device(mgpu_ctx *ctx, const struct mgpu_msg *d_msgs, uint64_t n, uint8_t *d_out, uint64_t cap, uint64_t *bytes);
@@ -643,6 +644,71 @@ int mgpu_beast_encode_gated(mgpu_ctx *ctx, const struct mgpu_msg *msgs, uint64_t
 int mgpu_beast_encode_gated_device(mgpu_ctx *ctx, const struct mgpu_msg *d_msgs, const uint8_t *d_verdict, uint64_t n, uint32_t flags,
                                    uint8_t *d_out, uint64_t cap, uint64_t *bytes, struct mgpu_deferred *d_deferred, uint64_t deferred_cap,
                                    uint64_t *ndeferred);
+
+/* The encoder with the aggregator's two options (mgpu_beast_encode_ex*): one sized argument block, so that later options need no new entry.
+ *   flags & MGPU_BEAST_VERBATIM (--net-verbatim, net_io.c:1662, 5846, 5863-5869): the payload bytes are raw[] — the frame as sliced —
+ *     instead of msg[]; length and type still come from msgbits.  The flag also lifts both forwarding tests (first-message suppression
+ *     and correctedbits < 2), so EVERY message of a carried length gets a frame: verdicts, if given, decide nothing, nothing is
+ *     deferred (*ndeferred = 0), and MGPU_BEAST_NET_RULE has no effect.
+ *   ids != NULL (--net-receiver-id, modesSendBeastOutput, net_io.c:1667-1680): one receiver id per message (mgpu_merge_by_time* writes
+ *     them).  Call a message a CALLER when the reference would call modesSendBeastOutput for it: a frame is due by flags and verdicts.
+ *     Before a caller's frame goes the prefix 0x1a 0xe3 + the id as 8 bytes big-endian, every 0x1a among them doubled (10 .. 18 bytes),
+ *     iff its id differs from the caller's before it; for the first caller, from *last_id (a fresh writer starts at 0, net_io.c:343: id
+ *     0 at the start gets no prefix).  On return *last_id is the last caller's id (unchanged without one): a list cut into several calls
+ *     with *last_id carried along gives the bytes of one call.  last_id == NULL stands for a fresh writer whose state is dropped.
+ *     As in the reference, a caller whose length the format does not carry writes NOTHING, not even a prefix, yet moves the writer's id
+ *     (the assignment at :1670 precedes the return at :1690 that skips completeWrite): the next frame of that same id has no prefix.
+ *   verdict (NULL: every message is a caller), flags & MGPU_BEAST_NET_RULE, deferred / deferred_cap / ndeferred: as in
+ *     mgpu_beast_encode_gated_device; ndeferred may be NULL without verdicts.  Unlike mgpu_beast_encode_gated the host-array form takes
+ *     the verdicts from the caller (mgpu_track_gate's), it does not run the gate.
+ *   ids together with MGPU_GATE_DEFER verdicts: a deferred message is not a caller.  It is listed as ever — index, and the offset at
+ *     which its frame (prefix first) would start — and the stream is exact for "every deferred message dropped".  A host that forwards a
+ *     deferred message cannot just splice its frame in: the prefixes behind it depend on it.  It has to encode again from that message
+ *     on with the verdict settled (MGPU_GATE_FORWARD), *last_id = the id of the last caller before it.
+ * With ids == NULL and without MGPU_BEAST_VERBATIM the result is that of the four entries above, which are thin calls into these.
+ * args->size = sizeof(struct mgpu_beast_args) of the caller's header (MGPU_E_INVAL if smaller than this library knows fields for).
+ * _device: msgs, verdict, ids, out and deferred are device pointers; last_id, bytes and ndeferred are host pointers in both forms. */
+#define MGPU_BEAST_VERBATIM 2u
+struct mgpu_beast_args {
+    uint32_t size;                     /* sizeof(struct mgpu_beast_args) */
+    uint32_t flags;                    /* MGPU_BEAST_NET_RULE | MGPU_BEAST_VERBATIM */
+    const struct mgpu_msg *msgs;
+    uint64_t n;
+    const uint8_t *verdict;            /* [n] or NULL */
+    const uint64_t *ids;               /* [n] or NULL */
+    uint64_t *last_id;                 /* host, in/out, or NULL */
+    uint8_t *out;
+    uint64_t cap;
+    uint64_t *bytes;                   /* host, out */
+    struct mgpu_deferred *deferred;    /* [deferred_cap] or NULL */
+    uint64_t deferred_cap;
+    uint64_t *ndeferred;               /* host, out; may be NULL without verdicts */
+};
+int mgpu_beast_encode_ex(mgpu_ctx *ctx, const struct mgpu_beast_args *args);
+int mgpu_beast_encode_ex_device(mgpu_ctx *ctx, const struct mgpu_beast_args *args);
+
+/* ---- the aggregator's time merge (kernels/merge.inc) ----------------------------------------------------------------------------
+ * nseg message lists (one per receiver) into ONE list ordered by timestamp — compared as a signed 64-bit integer — with equal stamps
+ * in input order: lower segment first, then position.  It is numpy's argsort(kind="stable") over the concatenation
+ * (readsb_amd/gather.py::merge_by_timestamp), whatever the input: the segments need not be sorted (with Mode A/C a receiver's list is
+ * only piecewise ordered).  This is the order a forwarder that merges N receivers writes in, and the per-message ids are what
+ * mgpu_beast_encode_ex* needs for --net-receiver-id (the consumer's side: readBeast's 0xe3 case in net_io.c; track.c:318-344, 588-642
+ * depend on it).
+ *   d_segments[k] / counts[k]: host arrays of nseg device pointers (16-byte aligned) and lengths; empty segments and n = 0 are valid.
+ *   segment_ids: host array of nseg ids, or NULL (ids 0).   d_verdict_in: host array of nseg device pointers to the segments' verdict
+ *   bytes (an entry may be NULL: zeros), or NULL.
+ *   d_out [n] merged records (must not overlap a segment);  optional (NULL: not wanted) d_perm [n] u64 = index of each output record in
+ *   the concatenation, d_ids [n] u64 = segment_ids[its segment], d_verdict_out [n] = its verdict byte.
+ * Limits: nseg <= 4096 (MGPU_E_INVAL beyond), n = sum of counts <= 2^32 - 1 (MGPU_E_CAPACITY beyond).  24 bytes of scratch per record
+ * belong to the context (allocated by the first call, grown on demand, freed by mgpu_destroy).  Runs on the stream the gate and the
+ * encoder use.  mgpu_merge_by_time: the same on host arrays (segments[k], verdict_in[k], out, perm, ids, verdict_out in host memory).
+ * mgpu_merge_last_passes: the 8-bit digit passes the last merge took (only those up to the highest bit its keys differed in: 0 .. 8). */
+int mgpu_merge_by_time_device(mgpu_ctx *ctx, const struct mgpu_msg *const *d_segments, const uint64_t *counts, uint32_t nseg,
+                              const uint64_t *segment_ids, const uint8_t *const *d_verdict_in, struct mgpu_msg *d_out, uint64_t *d_perm,
+                              uint64_t *d_ids, uint8_t *d_verdict_out);
+int mgpu_merge_by_time(mgpu_ctx *ctx, const struct mgpu_msg *const *segments, const uint64_t *counts, uint32_t nseg, const uint64_t *segment_ids,
+                       const uint8_t *const *verdict_in, struct mgpu_msg *out, uint64_t *perm, uint64_t *ids, uint8_t *verdict_out);
+int mgpu_merge_last_passes(mgpu_ctx *ctx);
 
 /* ---- position decode: CPR pairing and cpr.c over the message list (kernels/cpr.inc) ---------------------------------------------
  * What updatePosition does with a position message before its plausibility checks, on the device, one record per message (same

@@ -145,6 +145,17 @@ class ShardStreamArgs(C.Structure):
 
 
 DEFERRED_DTYPE = np.dtype([("index", "<u8"), ("offset", "<u8")])     # struct mgpu_deferred
+BEAST_NET_RULE, BEAST_VERBATIM = 1, 2                                 # MGPU_BEAST_*
+BEAST_FRAME_MAX = 44                                                  # bytes of a frame; with receiver ids up to 18 more for the prefix
+BEAST_PREFIX_MAX = 18
+MERGE_MAX_SEGMENTS = 4096
+
+
+class BeastArgs(C.Structure):                                         # struct mgpu_beast_args
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("msgs", C.c_void_p), ("n", C.c_uint64), ("verdict", C.c_void_p),
+                ("ids", C.c_void_p), ("last_id", C.POINTER(C.c_uint64)), ("out", C.c_void_p), ("cap", C.c_uint64),
+                ("bytes", C.POINTER(C.c_uint64)), ("deferred", C.c_void_p), ("deferred_cap", C.c_uint64),
+                ("ndeferred", C.POINTER(C.c_uint64))]
 ABI_VERSION = 6                             # MGPU_ABI_VERSION of the include/modes_gpu.h these ctypes mirrors were written against
 
 
@@ -316,6 +327,11 @@ def load_library():
     lib.mgpu_beast_encode_gated.argtypes = [vp, vp, u64, u32, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64)]
     lib.mgpu_beast_encode_gated_device.argtypes = [vp, vp, vp, u64, u32, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64)]
     lib.mgpu_beast_encode_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
+    lib.mgpu_beast_encode_ex.argtypes = [vp, C.POINTER(BeastArgs)]
+    lib.mgpu_beast_encode_ex_device.argtypes = [vp, C.POINTER(BeastArgs)]
+    lib.mgpu_merge_by_time.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
+    lib.mgpu_merge_by_time_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
+    lib.mgpu_merge_last_passes.argtypes = [vp]
     lib.mgpu_shard_begin.argtypes = [vp, u64, vp, i32]
     lib.mgpu_adder_bitmap_get.argtypes = [vp, vp]
     lib.mgpu_adder_bitmap_set.argtypes = [vp, vp]
@@ -586,8 +602,15 @@ class Demodulator:
         self._chk(self.lib.mgpu_track_gate(self.ctx, C.c_void_p(msgs.ctypes.data), len(msgs), C.c_void_p(out.ctypes.data)), "mgpu_track_gate")
         return out
 
-    def beast_encode_gated(self, msgs, net_rule=False, deferred_cap=None):
-        """mgpu_beast_encode_gated: -> (the beast stream of the certainly-forwarded messages, deferred[] records {index, offset})."""
+    def beast_encode_gated(self, msgs, net_rule=False, deferred_cap=None, verbatim=False, receiver_ids=None, last_id=0):
+        """mgpu_beast_encode_gated: -> (the beast stream of the certainly-forwarded messages, deferred[] records {index, offset}).
+        verbatim / receiver_ids / last_id: the gate's verdicts (track_gate, continuing the aircraft table just the same) through
+        beast_encode_ex; with receiver_ids the result has the writer's id behind the list as a third member."""
+        if verbatim or receiver_ids is not None:
+            verdict = self.track_gate(msgs)
+            stream, deferred, last = self.beast_encode_ex(msgs, verdict=verdict, net_rule=net_rule, verbatim=verbatim, ids=receiver_ids, last_id=last_id,
+                                                          deferred_cap=deferred_cap)
+            return (stream, deferred) if receiver_ids is None else (stream, deferred, last)
         msgs = np.ascontiguousarray(msgs)
         n = len(msgs)
         cap = n * 44 + 64
@@ -642,8 +665,12 @@ class Demodulator:
     def cpr_decode_device(self, d_cases_ptr, n, d_out_ptr):
         self._chk(self.lib.mgpu_cpr_decode_device(self.ctx, C.c_void_p(d_cases_ptr), n, C.c_void_p(d_out_ptr)), "mgpu_cpr_decode_device")
 
-    def beast_encode(self, msgs):
-        """Beast wire stream (bytes) of a record array (host memory in, host memory out, encoded on the GPU)."""
+    def beast_encode(self, msgs, verbatim=False, receiver_ids=None, last_id=0):
+        """Beast wire stream (bytes) of a record array (host memory in, host memory out, encoded on the GPU).  verbatim /
+        receiver_ids / last_id: beast_encode_ex's; with receiver_ids the result is (bytes, the writer's id behind the list)."""
+        if verbatim or receiver_ids is not None:
+            stream, _, last = self.beast_encode_ex(msgs, verbatim=verbatim, ids=receiver_ids, last_id=last_id)
+            return stream if receiver_ids is None else (stream, last)
         msgs = np.ascontiguousarray(msgs)
         assert msgs.dtype == MSG_DTYPE
         out = np.empty(len(msgs) * 44 + 64, dtype=np.uint8)
@@ -651,6 +678,87 @@ class Demodulator:
         self._chk(self.lib.mgpu_beast_encode(self.ctx, C.c_void_p(msgs.ctypes.data), len(msgs), C.c_void_p(out.ctypes.data), out.size, C.byref(nb)),
                   "mgpu_beast_encode")
         return out[: nb.value].tobytes()
+
+    @staticmethod
+    def _beast_flags(net_rule, verbatim):
+        return (BEAST_NET_RULE if net_rule else 0) | (BEAST_VERBATIM if verbatim else 0)
+
+    def beast_encode_ex(self, msgs, verdict=None, net_rule=False, verbatim=False, ids=None, last_id=0, deferred_cap=None):
+        """mgpu_beast_encode_ex on host arrays: the encoder with --net-verbatim (payload from raw[], every carried message framed) and
+        --net-receiver-id (ids: one u64 per message; last_id: the writer's id before the list, 0 for a fresh one).  verdict: the
+        caller's gate bytes or None (every message).  -> (stream bytes, deferred[] records, the writer's id behind the list)."""
+        msgs = np.ascontiguousarray(msgs)
+        assert msgs.dtype == MSG_DTYPE
+        n = len(msgs)
+        cap = n * (BEAST_FRAME_MAX + (BEAST_PREFIX_MAX if ids is not None else 0)) + 64
+        out = np.empty(cap, dtype=np.uint8)
+        dcap = int(deferred_cap if deferred_cap is not None else (n if verdict is not None else 0))
+        deferred = np.zeros(max(dcap, 1), dtype=DEFERRED_DTYPE)
+        if verdict is not None:
+            verdict = np.ascontiguousarray(verdict, dtype=np.uint8)
+            assert len(verdict) == n
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.uint64)
+            assert len(ids) == n
+        nb, nd, last = C.c_uint64(0), C.c_uint64(0), C.c_uint64(int(last_id))
+        a = BeastArgs(C.sizeof(BeastArgs), self._beast_flags(net_rule, verbatim), msgs.ctypes.data, n,
+                      verdict.ctypes.data if verdict is not None else None, ids.ctypes.data if ids is not None else None, C.pointer(last),
+                      out.ctypes.data, cap, C.pointer(nb), deferred.ctypes.data, dcap, C.pointer(nd))
+        self._chk(self.lib.mgpu_beast_encode_ex(self.ctx, C.byref(a)), "mgpu_beast_encode_ex")
+        return out[: nb.value].tobytes(), deferred[: nd.value].copy(), int(last.value)
+
+    def beast_encode_ex_device(self, d_msgs_ptr, n, d_out_ptr, cap, d_verdict_ptr=None, net_rule=False, verbatim=False, d_ids_ptr=None, last_id=0,
+                               d_deferred_ptr=None, deferred_cap=0):
+        """mgpu_beast_encode_ex_device: everything in HBM (pointers as ints).  -> (the stream's size in bytes, the number of
+        deferred messages, the writer's id behind the list)."""
+        nb, nd, last = C.c_uint64(0), C.c_uint64(0), C.c_uint64(int(last_id))
+        a = BeastArgs(C.sizeof(BeastArgs), self._beast_flags(net_rule, verbatim), d_msgs_ptr, n, d_verdict_ptr, d_ids_ptr, C.pointer(last), d_out_ptr, cap,
+                      C.pointer(nb), d_deferred_ptr, deferred_cap, C.pointer(nd))
+        self._chk(self.lib.mgpu_beast_encode_ex_device(self.ctx, C.byref(a)), "mgpu_beast_encode_ex_device")
+        return int(nb.value), int(nd.value), int(last.value)
+
+    def merge_by_time(self, lists, ids=None, verdicts=None):
+        """mgpu_merge_by_time on host arrays: the receivers' lists merged by timestamp on the GPU, equal stamps in input order —
+        gather.merge_by_timestamp's result.  ids: one receiver id per list, verdicts: one byte array per list (or None).
+        -> (merged records, permutation into the concatenation, id per record, verdict per record or None)."""
+        lists = [np.ascontiguousarray(m) for m in lists]
+        assert all(m.dtype == MSG_DTYPE for m in lists)
+        nseg, n = len(lists), sum(len(m) for m in lists)
+        ptrs = (C.c_void_p * max(nseg, 1))(*[m.ctypes.data for m in lists])
+        counts = np.array([len(m) for m in lists], dtype=np.uint64)
+        seg_ids = np.ascontiguousarray(ids if ids is not None else np.zeros(nseg), dtype=np.uint64)
+        assert len(seg_ids) == nseg
+        vptrs = None
+        if verdicts is not None:
+            verdicts = [np.ascontiguousarray(v, dtype=np.uint8) for v in verdicts]
+            assert [len(v) for v in verdicts] == [len(m) for m in lists]
+            vptrs = (C.c_void_p * max(nseg, 1))(*[v.ctypes.data for v in verdicts])
+        out, perm, oid = np.empty(n, dtype=MSG_DTYPE), np.empty(n, dtype=np.uint64), np.empty(n, dtype=np.uint64)
+        vout = np.empty(n, dtype=np.uint8) if verdicts is not None else None
+        self._chk(self.lib.mgpu_merge_by_time(self.ctx, C.cast(ptrs, C.c_void_p), C.c_void_p(counts.ctypes.data), nseg, C.c_void_p(seg_ids.ctypes.data),
+                                              C.cast(vptrs, C.c_void_p) if vptrs is not None else None, C.c_void_p(out.ctypes.data),
+                                              C.c_void_p(perm.ctypes.data), C.c_void_p(oid.ctypes.data),
+                                              C.c_void_p(vout.ctypes.data) if vout is not None else None), "mgpu_merge_by_time")
+        return out, perm, oid, vout
+
+    def merge_by_time_device(self, d_segment_ptrs, counts, d_out_ptr, ids=None, d_verdict_ptrs=None, d_perm_ptr=None, d_ids_ptr=None, d_verdict_out_ptr=None):
+        """mgpu_merge_by_time_device: d_segment_ptrs / counts = one device pointer (int) and one length per list; the merged records go
+        to d_out_ptr, optionally the permutation / ids (u64 each) / verdict bytes to the other pointers.  -> the number of records."""
+        nseg = len(counts)
+        assert len(d_segment_ptrs) == nseg
+        ptrs = (C.c_void_p * max(nseg, 1))(*[int(p) if p else None for p in d_segment_ptrs])
+        cnt = np.array([int(k) for k in counts], dtype=np.uint64)
+        seg_ids = np.ascontiguousarray(ids if ids is not None else np.zeros(nseg), dtype=np.uint64)
+        assert len(seg_ids) == nseg
+        vptrs = (C.c_void_p * max(nseg, 1))(*[int(p) if p else None for p in d_verdict_ptrs]) if d_verdict_ptrs is not None else None
+        self._chk(self.lib.mgpu_merge_by_time_device(self.ctx, C.cast(ptrs, C.c_void_p), C.c_void_p(cnt.ctypes.data), nseg, C.c_void_p(seg_ids.ctypes.data),
+                                                     C.cast(vptrs, C.c_void_p) if vptrs is not None else None, C.c_void_p(d_out_ptr), C.c_void_p(d_perm_ptr),
+                                                     C.c_void_p(d_ids_ptr), C.c_void_p(d_verdict_out_ptr)), "mgpu_merge_by_time_device")
+        return int(cnt.sum())
+
+    def merge_last_passes(self):
+        """8-bit digit passes the last merge took (those up to the highest bit in which its stamps differed)."""
+        return int(self.lib.mgpu_merge_last_passes(self.ctx))
 
     def beast_encode_device(self, d_msgs_ptr, n, d_out_ptr, cap):
         """Same on device pointers (ints, e.g. torch tensor.data_ptr()); returns the stream's size in bytes."""

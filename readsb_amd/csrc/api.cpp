@@ -501,7 +501,7 @@ void mgpu_destroy(mgpu_ctx *c) {
     }
     for (hipEvent_t e : c->ev_iq_read)
         if (e) (void) hipEventDestroy(e);
-    void *dev[] = {c->d_cpr_table, c->d_cpr_scratch, c->d_cpr_out, c->d_cpr_cases, c->d_deferred, c->d_gate_table, c->d_gate_scratch, c->d_gate_verdict, c->d_roll_tan, c->d_fields, c->d_beast_off, c->d_beast_len, c->d_beast_in, c->d_beast_out, c->d_beast_blocks, c->d_beast_total, c->d_hist, c->d_hist_iq, c->d_hist_sums, c->d_iq, c->d_win, c->d_adder_bitmap, c->d_bit_syndrome, c->d_group_syndrome, c->d_parity,
+    void *dev[] = {c->d_merge_scratch, c->d_merge_out, c->d_beast_idw, c->d_beast_ids, c->d_beast_verdict, c->d_cpr_table, c->d_cpr_scratch, c->d_cpr_out, c->d_cpr_cases, c->d_deferred, c->d_gate_table, c->d_gate_scratch, c->d_gate_verdict, c->d_roll_tan, c->d_fields, c->d_beast_off, c->d_beast_len, c->d_beast_in, c->d_beast_out, c->d_beast_blocks, c->d_beast_total, c->d_hist, c->d_hist_iq, c->d_hist_sums, c->d_iq, c->d_win, c->d_adder_bitmap, c->d_bit_syndrome, c->d_group_syndrome, c->d_parity,
                    c->d_tab_long, c->d_tab_short, c->d_uc8_folded};
     for (void *p : dev)
         if (p) (void) hipFree(p);

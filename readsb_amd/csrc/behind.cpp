@@ -21,25 +21,43 @@ static int beast_reserve(mgpu_ctx *c, uint64_t n) {
         HIPCHK(c, hipMalloc(&c->d_beast_off, 2 * (want / kBlock + 2) * sizeof(unsigned long long)));
         c->beast_cap_msgs = want;
     }
-    if (!c->d_beast_total) HIPCHK(c, hipMalloc(&c->d_beast_total, 2 * sizeof(unsigned long long)));
+    if (!c->d_beast_total) HIPCHK(c, hipMalloc(&c->d_beast_total, 4 * sizeof(unsigned long long)));   // bytes, deferred, last id
     return MGPU_OK;
 }
 
-// d_verdict == nullptr: every message's frame.  Everything in device memory; *ndeferred (may be null without a verdict)
+// grow-on-demand device scratch of the context
+static int reserve_bytes(mgpu_ctx *c, void **p, uint64_t *cap, uint64_t want) {
+    if (want <= *cap) return MGPU_OK;
+    if (*p) (void) hipFree(*p);
+    *p = nullptr; *cap = 0;
+    want += want / 4 + 1024;
+    HIPCHK(c, hipMalloc(p, want));
+    *cap = want;
+    return MGPU_OK;
+}
+
+// d_verdict == nullptr: every message's frame.  Everything in device memory; *ndeferred (may be null without a verdict).
+// d_ids / *last_id (host, may be null): the receiver-id prefixes; MGPU_BEAST_VERBATIM in flags (include/modes_gpu.h)
 static int beast_encode_dev(mgpu_ctx *c, const mgpu_msg *d_msgs, const uint8_t *d_verdict, uint64_t n, uint32_t flags, uint8_t *d_out, uint64_t cap,
-                            uint64_t *bytes, mgpu_deferred *d_deferred, uint64_t deferred_cap, uint64_t *ndeferred) {
+                            uint64_t *bytes, mgpu_deferred *d_deferred, uint64_t deferred_cap, uint64_t *ndeferred, const uint64_t *d_ids = nullptr,
+                            uint64_t *last_id = nullptr) {
     if (int rc = beast_reserve(c, n)) return rc;
+    if (d_ids)
+        if (int rc = reserve_bytes(c, &c->d_beast_idw, &c->beast_cap_idw, beast_id_scratch_bytes(n))) return rc;
+    const bool verbatim = (flags & MGPU_BEAST_VERBATIM) != 0, gated = d_verdict && !verbatim;
     const size_t nb = (size_t) (c->beast_cap_msgs / kBlock + 2);
     launch_beast_encode(d_msgs, n, c->d_beast_len, c->d_beast_blocks, c->d_beast_off, d_out, cap, c->d_beast_total, c->stream_aux, d_verdict,
-                        (flags & MGPU_BEAST_NET_RULE) ? 1 : 0, c->d_beast_blocks + nb, c->d_beast_off + nb, d_deferred, deferred_cap);
+                        (flags & MGPU_BEAST_NET_RULE) ? 1 : 0, c->d_beast_blocks + nb, c->d_beast_off + nb, d_deferred, deferred_cap, verbatim ? 1 : 0,
+                        (const unsigned long long *) d_ids, last_id ? *last_id : 0ull, c->d_beast_idw);
     HIPCHK(c, hipGetLastError());
-    unsigned long long total[2] = {0, 0};
-    HIPCHK(c, hipMemcpyAsync(total, c->d_beast_total, (d_verdict ? 2 : 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream_aux));
+    unsigned long long total[3] = {0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(total, c->d_beast_total, (d_ids ? 3 : gated ? 2 : 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream_aux));
     HIPCHK(c, hipStreamSynchronize(c->stream_aux));
     *bytes = total[0];
-    if (ndeferred) *ndeferred = total[1];
+    if (ndeferred) *ndeferred = gated ? total[1] : 0;
+    if (d_ids && last_id) *last_id = total[2];
     if (total[0] > cap) { c->err = "mgpu_beast_encode: output buffer too small"; return MGPU_E_OVERFLOW; }
-    if (d_verdict && total[1] > deferred_cap) { c->err = "mgpu_beast_encode_gated: more deferred messages than the list holds"; return MGPU_E_OVERFLOW; }
+    if (gated && total[1] > deferred_cap) { c->err = "mgpu_beast_encode_gated: more deferred messages than the list holds"; return MGPU_E_OVERFLOW; }
     return MGPU_OK;
 }
 
@@ -94,6 +112,158 @@ int mgpu_beast_encode(mgpu_ctx *c, const struct mgpu_msg *msgs, uint64_t n, uint
     HIPCHK(c, hipMemcpy(out, c->d_beast_out, *bytes, hipMemcpyDeviceToHost));
     return MGPU_OK;
 }
+
+// ---- the encoder with receiver ids and --net-verbatim (include/modes_gpu.h) ----
+static bool beast_args_ok(const struct mgpu_beast_args *a) {
+    if (!a || a->size < sizeof(struct mgpu_beast_args) || !a->bytes) return false;
+    if (a->flags & ~(MGPU_BEAST_NET_RULE | MGPU_BEAST_VERBATIM)) return false;
+    if (a->n && (!a->msgs || !a->out)) return false;
+    const bool gated = a->verdict && !(a->flags & MGPU_BEAST_VERBATIM);
+    if (gated && (!a->ndeferred || (a->deferred_cap && !a->deferred))) return false;
+    return true;
+}
+
+int mgpu_beast_encode_ex_device(mgpu_ctx *c, const struct mgpu_beast_args *a) {
+    if (!c || !beast_args_ok(a)) return MGPU_E_INVAL;
+    *a->bytes = 0;
+    if (a->ndeferred) *a->ndeferred = 0;
+    if (a->n == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return beast_encode_dev(c, a->msgs, a->verdict, a->n, a->flags, a->out, a->cap, a->bytes, a->deferred, a->deferred_cap, a->ndeferred, a->ids, a->last_id);
+}
+
+int mgpu_beast_encode_ex(mgpu_ctx *c, const struct mgpu_beast_args *a) {
+    if (!c || !beast_args_ok(a)) return MGPU_E_INVAL;
+    *a->bytes = 0;
+    if (a->ndeferred) *a->ndeferred = 0;
+    const uint64_t n = a->n;
+    if (n == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (int rc = stage_messages(c, a->msgs, n)) return rc;
+    if (int rc = reserve_beast_out(c, a->cap)) return rc;
+    const bool gated = a->verdict && !(a->flags & MGPU_BEAST_VERBATIM);
+    if (gated) {
+        if (int rc = reserve_bytes(c, &c->d_beast_verdict, &c->beast_cap_verdict, n)) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->d_beast_verdict, a->verdict, n, hipMemcpyHostToDevice, c->stream_aux));
+        if (a->deferred_cap + 64 > c->deferred_cap) {
+            if (c->d_deferred) (void) hipFree(c->d_deferred);
+            c->d_deferred = nullptr; c->deferred_cap = 0;
+            HIPCHK(c, hipMalloc(&c->d_deferred, (a->deferred_cap + 64) * sizeof(mgpu_deferred)));
+            c->deferred_cap = a->deferred_cap + 64;
+        }
+    }
+    if (a->ids) {
+        if (int rc = reserve_bytes(c, &c->d_beast_ids, &c->beast_cap_ids, n * sizeof(uint64_t))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->d_beast_ids, a->ids, n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream_aux));
+    }
+    const int rc = beast_encode_dev(c, (const mgpu_msg *) c->d_beast_in, gated ? (const uint8_t *) c->d_beast_verdict : nullptr, n, a->flags, c->d_beast_out, a->cap,
+                                    a->bytes, c->d_deferred, a->deferred_cap, a->ndeferred, a->ids ? (const uint64_t *) c->d_beast_ids : nullptr, a->last_id);
+    if (rc != MGPU_OK) return rc;
+    HIPCHK(c, hipMemcpy(a->out, c->d_beast_out, *a->bytes, hipMemcpyDeviceToHost));
+    if (gated && *a->ndeferred) HIPCHK(c, hipMemcpy(a->deferred, c->d_deferred, *a->ndeferred * sizeof(mgpu_deferred), hipMemcpyDeviceToHost));
+    return MGPU_OK;
+}
+
+// ---- the aggregator's time merge (kernels/merge.inc) ----
+
+static int merge_dev(mgpu_ctx *c, const struct mgpu_msg *const *d_segments, const uint64_t *counts, uint32_t nseg, const uint64_t *segment_ids,
+                     const uint8_t *const *d_verdict_in, struct mgpu_msg *d_out, uint64_t *d_perm, uint64_t *d_ids, uint8_t *d_verdict_out, uint64_t n) {
+    std::vector<MergeSeg> segs(nseg);
+    uint64_t start = 0;
+    for (uint32_t k = 0; k < nseg; ++k) {
+        segs[k].msgs = d_segments[k];
+        segs[k].verdict = d_verdict_in ? d_verdict_in[k] : nullptr;
+        segs[k].start = start;
+        segs[k].id = segment_ids ? segment_ids[k] : 0;
+        start += counts[k];
+    }
+    if (int rc = reserve_bytes(c, &c->d_merge_scratch, &c->merge_cap_scratch, merge_scratch_bytes(n, nseg))) return rc;
+    const unsigned long long *d_diff = launch_merge_keys(segs.data(), nseg, n, c->d_merge_scratch, c->stream_aux);
+    HIPCHK(c, hipGetLastError());
+    unsigned long long diff = 0;
+    HIPCHK(c, hipMemcpyAsync(&diff, d_diff, sizeof diff, hipMemcpyDeviceToHost, c->stream_aux));
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));            // (the segment table has left `segs` by now, too)
+    c->merge_passes = launch_merge_sort(nseg, n, diff, c->d_merge_scratch, d_out, d_perm, d_ids, d_verdict_out, c->stream_aux);
+    HIPCHK(c, hipGetLastError());
+    return MGPU_OK;
+}
+
+// the arguments both forms check; *n = the sum of the counts
+static int merge_args(mgpu_ctx *c, const struct mgpu_msg *const *segments, const uint64_t *counts, uint32_t nseg, const uint8_t *const *verdict_in,
+                      const void *out, const void *verdict_out, uint64_t *n) {
+    if (!c || nseg > kMergeMaxSeg || (nseg && (!segments || !counts))) return MGPU_E_INVAL;
+    uint64_t sum = 0;
+    for (uint32_t k = 0; k < nseg; ++k) {
+        if (counts[k] > 0xffffffffull) { c->err = "mgpu_merge_by_time: more than 2^32 - 1 records"; return MGPU_E_CAPACITY; }
+        sum += counts[k];
+        if (counts[k] && (!segments[k] || ((uintptr_t) segments[k] & 15u))) return MGPU_E_INVAL;
+    }
+    if (sum > 0xffffffffull) { c->err = "mgpu_merge_by_time: more than 2^32 - 1 records"; return MGPU_E_CAPACITY; }
+    if (sum && (!out || (verdict_out && !verdict_in))) return MGPU_E_INVAL;
+    *n = sum;
+    return MGPU_OK;
+}
+
+int mgpu_merge_by_time_device(mgpu_ctx *c, const struct mgpu_msg *const *d_segments, const uint64_t *counts, uint32_t nseg, const uint64_t *segment_ids,
+                              const uint8_t *const *d_verdict_in, struct mgpu_msg *d_out, uint64_t *d_perm, uint64_t *d_ids, uint8_t *d_verdict_out) {
+    uint64_t n = 0;
+    if (int rc = merge_args(c, d_segments, counts, nseg, d_verdict_in, d_out, d_verdict_out, &n)) return rc;
+    c->merge_passes = 0;
+    if (n == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (int rc = merge_dev(c, d_segments, counts, nseg, segment_ids, d_verdict_in, d_out, d_perm, d_ids, d_verdict_out, n)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    return MGPU_OK;
+}
+
+int mgpu_merge_by_time(mgpu_ctx *c, const struct mgpu_msg *const *segments, const uint64_t *counts, uint32_t nseg, const uint64_t *segment_ids,
+                       const uint8_t *const *verdict_in, struct mgpu_msg *out, uint64_t *perm, uint64_t *ids, uint8_t *verdict_out) {
+    uint64_t n = 0;
+    if (int rc = merge_args(c, segments, counts, nseg, verdict_in, out, verdict_out, &n)) return rc;
+    c->merge_passes = 0;
+    if (n == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    // staged: the concatenation in d_beast_in, its verdicts in d_beast_verdict; results: records | permutation | ids | verdicts in d_merge_out
+    if (n * sizeof(mgpu_msg) > c->beast_cap_in) {
+        if (c->d_beast_in) (void) hipFree(c->d_beast_in);
+        c->d_beast_in = nullptr; c->beast_cap_in = 0;
+        const uint64_t want = (n + n / 4 + 1024) * sizeof(mgpu_msg);
+        HIPCHK(c, hipMalloc(&c->d_beast_in, want));
+        c->beast_cap_in = want;
+    }
+    if (verdict_in)
+        if (int rc = reserve_bytes(c, &c->d_beast_verdict, &c->beast_cap_verdict, n)) return rc;
+    if (int rc = reserve_bytes(c, &c->d_merge_out, &c->merge_cap_out, n * (sizeof(mgpu_msg) + 8 + 8 + 1))) return rc;
+    std::vector<const mgpu_msg *> d_seg(nseg);
+    std::vector<const uint8_t *> d_ver(nseg);
+    uint64_t at = 0;
+    for (uint32_t k = 0; k < nseg; ++k) {
+        d_seg[k] = (const mgpu_msg *) c->d_beast_in + at;
+        d_ver[k] = nullptr;
+        if (counts[k]) {
+            HIPCHK(c, hipMemcpyAsync(c->d_beast_in + at * sizeof(mgpu_msg), segments[k], counts[k] * sizeof(mgpu_msg), hipMemcpyHostToDevice, c->stream_aux));
+            if (verdict_in && verdict_in[k]) {
+                d_ver[k] = (const uint8_t *) c->d_beast_verdict + at;
+                HIPCHK(c, hipMemcpyAsync((uint8_t *) c->d_beast_verdict + at, verdict_in[k], counts[k], hipMemcpyHostToDevice, c->stream_aux));
+            }
+        }
+        at += counts[k];
+    }
+    mgpu_msg *d_out = (mgpu_msg *) c->d_merge_out;
+    uint64_t *d_perm = (uint64_t *) (d_out + n), *d_ids = d_perm + n;
+    uint8_t *d_vout = (uint8_t *) (d_ids + n);
+    if (int rc = merge_dev(c, d_seg.data(), counts, nseg, segment_ids, verdict_in ? d_ver.data() : nullptr, d_out, perm ? d_perm : nullptr, ids ? d_ids : nullptr,
+                           verdict_out ? d_vout : nullptr, n))
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(out, d_out, n * sizeof(mgpu_msg), hipMemcpyDeviceToHost, c->stream_aux));
+    if (perm) HIPCHK(c, hipMemcpyAsync(perm, d_perm, n * 8, hipMemcpyDeviceToHost, c->stream_aux));
+    if (ids) HIPCHK(c, hipMemcpyAsync(ids, d_ids, n * 8, hipMemcpyDeviceToHost, c->stream_aux));
+    if (verdict_out) HIPCHK(c, hipMemcpyAsync(verdict_out, d_vout, n, hipMemcpyDeviceToHost, c->stream_aux));
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    return MGPU_OK;
+}
+
+int mgpu_merge_last_passes(mgpu_ctx *c) { return c ? c->merge_passes : MGPU_E_INVAL; }
 
 // ---- per-message field decode (mode_s.c:598-760, 806-1555; mode_ac.c:171-200) --------------------------------------
 

@@ -431,6 +431,13 @@ struct mgpu_ctx {
     hipStream_t stream_aux = nullptr;                         // field decode / beast encoder / tracking gate: synchronous calls, not behind the pipeline's queued chunks
     unsigned long long *d_beast_total = nullptr;
     uint64_t beast_cap_msgs = 0, beast_cap_in = 0, beast_cap_out = 0;
+    // receiver ids in the encoder (mgpu_beast_encode_ex*): the per-workgroup summaries; the host-array form's staged ids and verdicts
+    void *d_beast_idw = nullptr, *d_beast_ids = nullptr, *d_beast_verdict = nullptr;
+    uint64_t beast_cap_idw = 0, beast_cap_ids = 0, beast_cap_verdict = 0;
+    // the time merge (kernels/merge.inc): its scratch; the host-array form's merged records | permutation | ids
+    void *d_merge_scratch = nullptr, *d_merge_out = nullptr;
+    uint64_t merge_cap_scratch = 0, merge_cap_out = 0;
+    int merge_passes = 0;                                     // digit passes of the last merge
     uint16_t *d_hist = nullptr;                               // magnitudes of the 326 samples before the shard
     uint8_t *d_hist_iq = nullptr;
     unsigned long long *d_hist_sums = nullptr;

@@ -205,7 +205,24 @@ void launch_modeac_scan(const uint16_t *mag, uint64_t n, uint32_t buf_samples, c
 void launch_decode_fields(const mgpu_msg *msgs, uint64_t n, mgpu_fields *out, const double *roll_tan, hipStream_t s);
 void launch_beast_encode(const mgpu_msg *msgs, uint64_t n, uint16_t *meta, uint32_t *block_bytes, unsigned long long *block_off, uint8_t *out,
                          uint64_t cap, unsigned long long *total /* [2]: bytes, deferred */, hipStream_t s, const uint8_t *verdict = nullptr, int net_rule = 0,
-                         uint32_t *block_def = nullptr, unsigned long long *block_def_off = nullptr, mgpu_deferred *deferred = nullptr, uint64_t def_cap = 0);
+                         uint32_t *block_def = nullptr, unsigned long long *block_def_off = nullptr, mgpu_deferred *deferred = nullptr, uint64_t def_cap = 0,
+                         int verbatim = 0, const unsigned long long *ids = nullptr /* per message: total[2] = the last caller's */,
+                         unsigned long long last_id = 0, void *id_scratch = nullptr /* beast_id_scratch_bytes(n), with ids */);
+size_t beast_id_scratch_bytes(uint64_t n);
+// stable merge of message lists by timestamp (kernels/merge.inc): segs [nseg] in device memory, scratch = merge_scratch_bytes(n, nseg)
+struct MergeSeg {
+    const mgpu_msg *msgs;
+    const uint8_t *verdict;       // may be null
+    uint64_t start;               // of the segment in the concatenation
+    uint64_t id;
+};
+constexpr uint32_t kMergeMaxSeg = 4096;
+size_t merge_scratch_bytes(uint64_t n, uint32_t nseg);
+// the two halves of a merge (n > 0): the keys + the bits they differ in (the returned device word), then — that word read back — the
+// digit passes up to its highest bit and the gather; returns the number of passes
+const unsigned long long *launch_merge_keys(const MergeSeg *h_segs, uint32_t nseg, uint64_t n, void *scratch, hipStream_t s);
+int launch_merge_sort(uint32_t nseg, uint64_t n, uint64_t diff, void *scratch, mgpu_msg *out, uint64_t *perm, uint64_t *ids, uint8_t *verdict_out,
+                      hipStream_t s);
 // first stage of the tracker + the forwarding rule over a message list in device memory (kernels/gate.inc): table = gate_table_bytes()
 // bytes, zeroed once and kept from call to call; scratch = gate_scratch_bytes(n); verdict: one byte per message (include/modes_gpu.h)
 size_t gate_table_bytes();

@@ -123,6 +123,7 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 #include "kernels/beast.inc"
 #include "kernels/fields.inc"
 #include "kernels/gate.inc"
+#include "kernels/merge.inc"
 #include "kernels/cpr.inc"
 
 }  // namespace mgpu

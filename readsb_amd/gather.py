@@ -213,8 +213,29 @@ class MessageGatherer:
         return counts, [recv[r][: counts[r] * self.rec].cpu().numpy().view(self.dtype).copy() for r in range(self.world)]
 
 
+    def merge_device(self, k=None, ids=None, demod=None):
+        """What wait() holds, merged by time in `dst`'s HBM (demod = the Demodulator whose context does it: merge_by_time_device; the ranks' buffers are the segments,
+        no copy): -> (n, uint8 device tensor of the n merged records, int64 device tensor of their receiver ids — ids[rank] per
+        record, the bits of the u64 — or None without ids); (0, None, None) on the other ranks.  The tensors are what
+        Demodulator.beast_encode_ex_device takes (data_ptr()); merge_by_timestamp is the same on the host, as the checker."""
+        if demod is None:
+            raise ValueError("merge_device: demod=<the Demodulator whose context runs the merge> is required")
+        counts, recv = self.wait(k)
+        if recv is None:
+            return 0, None, None
+        if self.device.type != "cuda":
+            raise RuntimeError("merge_device: the gathered records are not in device memory")
+        n = sum(counts)
+        out = torch.empty(max(n, 1) * self.rec, dtype=torch.uint8, device=self.device)
+        out_ids = torch.empty(max(n, 1), dtype=torch.int64, device=self.device) if ids is not None else None
+        demod.merge_by_time_device([int(t.data_ptr()) for t in recv], counts, int(out.data_ptr()), ids=ids,
+                                   d_ids_ptr=int(out_ids.data_ptr()) if out_ids is not None else None)
+        return n, out[: n * self.rec], (out_ids[:n] if out_ids is not None else None)
+
+
 def merge_by_timestamp(per_rank):
-    """Rank-0 side: one list ordered by the 12 MHz timestamp (stable for equal stamps)."""
+    """Rank-0 side: one list ordered by the 12 MHz timestamp (stable for equal stamps).  The host checker of
+    MessageGatherer.merge_device / mgpu_merge_by_time*."""
     allm = np.concatenate(per_rank) if per_rank else np.zeros(0)
     order = np.argsort(allm["timestamp"], kind="stable")
     return allm[order]

@@ -15,6 +15,15 @@
  *                     [--fix|--no-fix|--aggressive] [--no-fix-df] [--preamble-threshold T] [--startup-time-ms T]
  *                     [--gpu-device D (default: rank)] [--out beast.bin (rank 0)]
  *                     [--forward-only [--net-rule] [--deferred-out deferred.bin]]
+ *                     [--merge] [--receiver-id HEX] [--verbatim]
+ *
+ * --merge: rank 0 merges the gathered lists by timestamp on its GPU (mgpu_merge_by_time_device, the ranks' parts of its buffer as the
+ * segments; equal stamps: lower rank first) and encodes the merged list — the order a forwarder of N receivers writes in.
+ * --receiver-id HEX (per rank, sent along with the rank's count): the stream carries modesSendBeastOutput's 0x1a 0xe3 receiverId prefix
+ * (--net-receiver-id, net_io.c:1667-1680) wherever the id changes, so the consumer attributes every message to its receiver; ranks that
+ * give none have id 0.  --verbatim: --net-verbatim (the frames as sliced, every message).  All three through mgpu_beast_encode_ex_device.
+ * With --forward-only the gate still runs per rank before the merge, the verdicts ride through it, and the deferred messages are left
+ * out and listed as before; with ids, a host that forwards one has to encode again from it on (include/modes_gpu.h).
  *
  * --forward-only (round 6): rank 0 writes what N reference receivers would have FORWARDED, not every accepted
  * message — per rank's record list (a receiver has its own tracker: the aircraft table is reset between ranks) field decode ->
@@ -89,7 +98,8 @@ int main(int argc, char **argv) {
     struct mgpu_config cfg;
     mgpu_config_defaults(&cfg);
     const char *ifile = NULL, *idfile = NULL, *outpath = NULL, *defpath = NULL;
-    int rank = 0, world = 1, device = -1, forward_only = 0, net_rule = 0;
+    int rank = 0, world = 1, device = -1, forward_only = 0, net_rule = 0, merge = 0, verbatim = 0, receiver_id_set = 0;
+    unsigned long long receiver_id = 0;
     const unsigned chunk_buffers = 512;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--ifile") && i + 1 < argc) ifile = argv[++i];
@@ -109,11 +119,21 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--out") && i + 1 < argc) outpath = argv[++i];
         else if (!strcmp(argv[i], "--forward-only")) forward_only = 1;
         else if (!strcmp(argv[i], "--net-rule")) net_rule = 1;
+        else if (!strcmp(argv[i], "--merge")) merge = 1;
+        else if (!strcmp(argv[i], "--verbatim")) verbatim = 1;
+        else if (!strcmp(argv[i], "--receiver-id") && i + 1 < argc) { receiver_id = strtoull(argv[++i], NULL, 16); receiver_id_set = 1; }
         else if (!strcmp(argv[i], "--deferred-out") && i + 1 < argc) defpath = argv[++i];
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (!ifile || !idfile || world < 1 || rank < 0 || rank >= world) {
-        fprintf(stderr, "usage: %s --rank R --world N --id-file PATH --ifile FILE [--iformat F] [--fix|--no-fix|--aggressive] [--out beast.bin]\n", argv[0]);
+        fprintf(stderr, "usage: %s --rank R --world N --id-file PATH --ifile FILE [--iformat F] [--fix|--no-fix|--aggressive] [--out beast.bin]\n"
+                        "       [--merge] [--receiver-id HEX] [--verbatim] [--forward-only [--net-rule] [--deferred-out FILE]]\n"
+                        "  --merge          rank 0 merges the ranks' messages by time on its GPU before encoding (equal stamps: lower rank first)\n"
+                        "  --receiver-id    this rank's 64-bit id; given on any rank, the stream carries the 0x1a 0xe3 prefix wherever the id changes\n"
+                        "  --verbatim       the frames as sliced (--net-verbatim): every message, --forward-only's verdicts decide nothing\n"
+                        "  --forward-only   with --merge the gate still runs per rank (one tracker per receiver) and the verdicts ride through the merge;\n"
+                        "                   deferred messages are left out of the stream and listed {rank, index, offset}: with ids, forwarding one\n"
+                        "                   means encoding again from it on (the prefixes behind it depend on it)\n", argv[0]);
         return 2;
     }
     cfg.device = device >= 0 ? device : rank;
@@ -159,15 +179,18 @@ int main(int argc, char **argv) {
     CHK_NCCL(ncclCommInitRank(&comm, world, id, rank));
     hipStream_t s;
     CHK_HIP(own_queue_stream(&s));
-    unsigned long long *d_counts = NULL, mine = nmsg;
-    CHK_HIP(hipMalloc((void **) &d_counts, (size_t) (world + 1) * sizeof(*d_counts)));
-    CHK_HIP(hipMemcpyAsync(d_counts + world, &mine, sizeof(mine), hipMemcpyHostToDevice, s));
-    CHK_NCCL(ncclAllGather(d_counts + world, d_counts, 1, ncclUint64, comm, s));
-    unsigned long long *counts = malloc((size_t) world * sizeof(*counts));
-    CHK_HIP(hipMemcpyAsync(counts, d_counts, (size_t) world * sizeof(*counts), hipMemcpyDeviceToHost, s));
+    unsigned long long *d_counts = NULL, mine[3] = {nmsg, receiver_id, (unsigned long long) receiver_id_set};   /* the id rides with the count */
+    CHK_HIP(hipMalloc((void **) &d_counts, (size_t) (world + 1) * sizeof(mine)));
+    CHK_HIP(hipMemcpyAsync(d_counts + 3 * world, mine, sizeof(mine), hipMemcpyHostToDevice, s));
+    CHK_NCCL(ncclAllGather(d_counts + 3 * world, d_counts, 3, ncclUint64, comm, s));
+    unsigned long long *gathered = malloc((size_t) world * sizeof(mine));
+    CHK_HIP(hipMemcpyAsync(gathered, d_counts, (size_t) world * sizeof(mine), hipMemcpyDeviceToHost, s));
     CHK_HIP(hipStreamSynchronize(s));
+    unsigned long long *counts = malloc((size_t) world * sizeof(*counts)), *rids = malloc((size_t) world * sizeof(*rids)),
+                       *rid_set = malloc((size_t) world * sizeof(*rid_set));
     uint64_t total = 0;
-    for (int r = 0; r < world; ++r) total += counts[r];
+    for (int r = 0; r < world; ++r) { counts[r] = gathered[3 * r]; rids[r] = gathered[3 * r + 1]; rid_set[r] = gathered[3 * r + 2]; total += counts[r]; }
+    free(gathered);
 
     struct mgpu_msg *d_mine = NULL, *d_all = NULL;
     CHK_HIP(hipMalloc((void **) &d_mine, (nmsg + 1) * sizeof(*d_mine)));
@@ -188,47 +211,102 @@ int main(int argc, char **argv) {
     /* ---- rank 0: one beast stream of everything, encoded where the records are ---- */
     int rc = 0;
     if (rank == 0) {
-        uint8_t *d_out = NULL;
-        const uint64_t out_cap = total * 48 + 64;                  /* a frame is at most 2 + 2*(6 + 1 + 14) bytes */
+        uint8_t *d_out = NULL, *d_verdict = NULL, *d_verdict_m = NULL;
+        uint64_t *d_ids = NULL, *d_perm = NULL, *h_perm = NULL;
+        struct mgpu_msg *d_merged = NULL;
+        const uint64_t out_cap = total * (48 + 18) + 64;           /* a frame is at most 2 + 2*(6 + 1 + 14) bytes, an id prefix 2 + 2*8 */
         CHK_HIP(hipMalloc((void **) &d_out, out_cap));
-        uint64_t bytes = 0, ndeferred_total = 0;
-        if (!forward_only) {
-            CHK_MGPU(mgpu_beast_encode_device(ctx, d_all, total, d_out, out_cap, &bytes), ctx);
-        } else {
+        uint64_t bytes = 0, ndeferred_total = 0, last_id = 0;
+        uint64_t *seg_ids = malloc((size_t) world * sizeof(*seg_ids)), *seg_counts = malloc((size_t) world * sizeof(*seg_counts));
+        uint64_t *seg_off = malloc((size_t) (world + 1) * sizeof(*seg_off));
+        const struct mgpu_msg **seg_ptr = malloc((size_t) world * sizeof(*seg_ptr));
+        const uint8_t **seg_ver = malloc((size_t) world * sizeof(*seg_ver));
+        int have_ids = 0;
+        seg_off[0] = 0;
+        for (int r = 0; r < world; ++r) {
+            seg_counts[r] = counts[r]; seg_ids[r] = rids[r]; have_ids |= rid_set[r] != 0;
+            seg_ptr[r] = d_all + seg_off[r];
+            seg_off[r + 1] = seg_off[r] + counts[r];
+        }
+        const uint32_t flags = (net_rule ? MGPU_BEAST_NET_RULE : 0u) | (verbatim ? MGPU_BEAST_VERBATIM : 0u);
+        struct mgpu_deferred *d_def = NULL, *h_def = NULL;
+        FILE *fd_def = NULL;
+        if (forward_only) {                                        /* the verdicts: every receiver has its own tracker */
             struct mgpu_fields *d_fields = NULL;
-            uint8_t *d_verdict = NULL;
-            struct mgpu_deferred *d_def = NULL, *h_def = malloc((size_t) (total + 1) * sizeof(*h_def));
             CHK_HIP(hipMalloc((void **) &d_fields, (size_t) (total + 1) * sizeof(*d_fields)));
             CHK_HIP(hipMalloc((void **) &d_verdict, (size_t) total + 1));
             CHK_HIP(hipMalloc((void **) &d_def, (size_t) (total + 1) * sizeof(*d_def)));
-            FILE *fd_def = defpath ? fopen(defpath, "wb") : NULL;
+            h_def = malloc((size_t) (total + 1) * sizeof(*h_def));
+            fd_def = defpath ? fopen(defpath, "wb") : NULL;
             if (defpath && !fd_def) { perror(defpath); return 1; }
-            uint64_t off = 0;
-            for (int r = 0; r < world; ++r) {                      /* every receiver has its own tracker */
-                const uint64_t n = counts[r];
-                if (n) {
-                    uint64_t nb = 0, nd = 0;
-                    CHK_MGPU(mgpu_track_gate_reset(ctx), ctx);
-                    CHK_MGPU(mgpu_decode_fields_device(ctx, d_all + off, n, d_fields), ctx);
-                    CHK_MGPU(mgpu_track_gate_device(ctx, d_all + off, d_fields, n, d_verdict), ctx);
-                    CHK_MGPU(mgpu_beast_encode_gated_device(ctx, d_all + off, d_verdict, n, net_rule ? MGPU_BEAST_NET_RULE : 0u, d_out + bytes,
-                                                            out_cap - bytes, &nb, d_def, n, &nd), ctx);
-                    if (nd && fd_def) {
-                        CHK_HIP(hipMemcpy(h_def, d_def, (size_t) nd * sizeof(*h_def), hipMemcpyDeviceToHost));
-                        for (uint64_t k = 0; k < nd; ++k) {
-                            const uint64_t rec[3] = {(uint64_t) r, h_def[k].index, bytes + h_def[k].offset};
-                            if (fwrite(rec, sizeof(rec), 1, fd_def) != 1) rc = 1;
-                        }
-                    }
-                    bytes += nb;
-                    ndeferred_total += nd;
-                }
-                off += n;
+            for (int r = 0; r < world; ++r) {
+                seg_ver[r] = d_verdict + seg_off[r];
+                if (!counts[r]) continue;
+                CHK_MGPU(mgpu_track_gate_reset(ctx), ctx);
+                CHK_MGPU(mgpu_decode_fields_device(ctx, seg_ptr[r], counts[r], d_fields), ctx);
+                CHK_MGPU(mgpu_track_gate_device(ctx, seg_ptr[r], d_fields, counts[r], d_verdict + seg_off[r]), ctx);
             }
-            if (fd_def) fclose(fd_def);
-            free(h_def);
-            (void) hipFree(d_def); (void) hipFree(d_verdict); (void) hipFree(d_fields);
+            (void) hipFree(d_fields);
         }
+        /* the list to encode: rank after rank, or (--merge) all ranks by time, ids and verdicts carried along */
+        const struct mgpu_msg *d_list = d_all;
+        const uint8_t *d_list_verdict = d_verdict;
+        if (have_ids) CHK_HIP(hipMalloc((void **) &d_ids, (size_t) (total + 1) * sizeof(*d_ids)));
+        if (merge) {
+            CHK_HIP(hipMalloc((void **) &d_merged, (size_t) (total + 1) * sizeof(*d_merged)));
+            if (forward_only) {
+                CHK_HIP(hipMalloc((void **) &d_verdict_m, (size_t) total + 1));
+                CHK_HIP(hipMalloc((void **) &d_perm, (size_t) (total + 1) * sizeof(*d_perm)));
+            }
+            CHK_MGPU(mgpu_merge_by_time_device(ctx, seg_ptr, seg_counts, (uint32_t) world, seg_ids, forward_only ? seg_ver : NULL, d_merged, d_perm, d_ids,
+                                               d_verdict_m), ctx);
+            d_list = d_merged; d_list_verdict = d_verdict_m;
+            if (d_perm) {
+                h_perm = malloc((size_t) (total + 1) * sizeof(*h_perm));
+                CHK_HIP(hipMemcpy(h_perm, d_perm, (size_t) total * sizeof(*h_perm), hipMemcpyDeviceToHost));
+            }
+        } else if (have_ids) {
+            uint64_t *h_ids = malloc((size_t) (total + 1) * sizeof(*h_ids));
+            for (int r = 0; r < world; ++r)
+                for (uint64_t k = seg_off[r]; k < seg_off[r + 1]; ++k) h_ids[k] = seg_ids[r];
+            CHK_HIP(hipMemcpy(d_ids, h_ids, (size_t) total * sizeof(*h_ids), hipMemcpyHostToDevice));
+            free(h_ids);
+        }
+        /* one call over the list; --forward-only without --merge: one call per rank, so that a deferred message names its rank's list */
+        const int pieces = (forward_only && !merge) ? world : 1;
+        for (int r = 0; r < pieces; ++r) {
+            const uint64_t off = pieces > 1 ? seg_off[r] : 0, n = pieces > 1 ? counts[r] : total;
+            if (!n) continue;
+            uint64_t nb = 0, nd = 0;
+            struct mgpu_beast_args a;
+            memset(&a, 0, sizeof(a));
+            a.size = (uint32_t) sizeof(a); a.flags = flags;
+            a.msgs = d_list + off; a.n = n;
+            a.verdict = forward_only ? d_list_verdict + off : NULL;
+            a.ids = d_ids ? d_ids + off : NULL; a.last_id = &last_id;
+            a.out = d_out + bytes; a.cap = out_cap - bytes; a.bytes = &nb;
+            a.deferred = d_def; a.deferred_cap = forward_only ? n : 0; a.ndeferred = &nd;
+            CHK_MGPU(mgpu_beast_encode_ex_device(ctx, &a), ctx);
+            if (nd && fd_def) {
+                CHK_HIP(hipMemcpy(h_def, d_def, (size_t) nd * sizeof(*h_def), hipMemcpyDeviceToHost));
+                for (uint64_t k = 0; k < nd; ++k) {
+                    uint64_t who = (uint64_t) r, idx = h_def[k].index;
+                    if (merge) {                                   /* through the permutation back to {rank, index in the rank's list} */
+                        const uint64_t src = h_perm[idx];
+                        who = 0;
+                        while (who + 1 < (uint64_t) world && seg_off[who + 1] <= src) ++who;
+                        idx = src - seg_off[who];
+                    }
+                    const uint64_t rec[3] = {who, idx, bytes + h_def[k].offset};
+                    if (fwrite(rec, sizeof(rec), 1, fd_def) != 1) rc = 1;
+                }
+            }
+            bytes += nb;
+            ndeferred_total += nd;
+        }
+        if (fd_def) fclose(fd_def);
+        free(h_def); free(h_perm); free(seg_ids); free(seg_counts); free(seg_off); free(seg_ptr); free(seg_ver);
+        (void) hipFree(d_def); (void) hipFree(d_verdict); (void) hipFree(d_verdict_m); (void) hipFree(d_perm); (void) hipFree(d_ids); (void) hipFree(d_merged);
         uint8_t *out = malloc(bytes + 1);
         CHK_HIP(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost));
         FILE *f = outpath ? fopen(outpath, "wb") : stdout;
@@ -246,7 +324,7 @@ int main(int argc, char **argv) {
     }
     (void) hipFree(d_mine);
     (void) hipFree(d_counts);
-    free(counts);
+    free(counts); free(rids); free(rid_set);
     free(msgs);
     ncclCommDestroy(comm);
     (void) hipStreamDestroy(s);

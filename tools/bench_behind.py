@@ -1,5 +1,7 @@
 """Throughput of the stages behind the message list — k_decode_fields, k_beast_size/k_beast_write, the tracking gate
-(mgpu_track_gate_device) and the position decode (mgpu_cpr_track_device) — on records resident in HBM
+(mgpu_track_gate_device), the position decode (mgpu_cpr_track_device), the aggregator's time merge (mgpu_merge_by_time_device, the
+list as 4 segments, with the digit passes it took) and the encoder with receiver ids that change on every message
+(mgpu_beast_encode_ex_device) — on records resident in HBM
 (python tools/bench_behind.py [--messages N]).  Prints one JSON line per stage: messages/s, algorithmic
 GB/s (64 + 176 B per message for the field decode; 64 B in + the frame bytes out for the encoder; for the gate and the
 position decode the records read and written once, 64 + 176 + 1 and 64 + 176 + 32 B, their sort's traffic not counted) against the
@@ -68,13 +70,42 @@ def main():
     for _ in range(a.reps):
         d.cpr_track_device(d_in.value, d_f.value, n, d_p.value, ref=ref)
     t_c = (time.perf_counter() - t0) / a.reps
+    # the aggregator's output: the list as 4 receivers' segments merged by time, then encoded with ids that change on every message
+    d_m, d_ids, d_bx = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    assert hip.hipMalloc(C.byref(d_m), n * 64) == 0 and hip.hipMalloc(C.byref(d_ids), n * 8) == 0 and hip.hipMalloc(C.byref(d_bx), n * 62 + 64) == 0
+    quarter = n // 4
+    segs, counts = [d_in.value + k * quarter * 64 for k in range(4)], [quarter, quarter, quarter, n - 3 * quarter]
+    for _ in range(2):
+        d.merge_by_time_device(segs, counts, d_m.value, ids=[1, 2, 3, 4], d_ids_ptr=d_ids.value)
+    t0 = time.perf_counter()
+    for _ in range(a.reps):
+        d.merge_by_time_device(segs, counts, d_m.value, ids=[1, 2, 3, 4], d_ids_ptr=d_ids.value)
+    t_m = (time.perf_counter() - t0) / a.reps
+    passes = d.merge_last_passes()
+    alt = (np.arange(1 << 20, dtype=np.uint64) & np.uint64(1)) + np.uint64(0x1A00000000000021)
+    for k in range(0, n, len(alt)):
+        assert hip.hipMemcpy(C.c_void_p(d_ids.value + k * 8), alt.ctypes.data, min(len(alt), n - k) * 8, 1) == 0
+    for _ in range(2):
+        nbytes_x = d.beast_encode_ex_device(d_in.value, n, d_bx.value, n * 62 + 64, d_ids_ptr=d_ids.value)[0]
+    t0 = time.perf_counter()
+    for _ in range(a.reps):
+        d.beast_encode_ex_device(d_in.value, n, d_bx.value, n * 62 + 64, d_ids_ptr=d_ids.value)
+    t_x = (time.perf_counter() - t0) / a.reps
+    # the plain encoder once more, behind everything else: run to run spread of the figure above
+    t0 = time.perf_counter()
+    for _ in range(a.reps):
+        d.beast_encode_device(d_in.value, n, d_b.value, n * 44)
+    t_b2 = (time.perf_counter() - t0) / a.reps
     pos = np.empty(len(m), dtype=readsb_amd.binding.POSITION_DTYPE)
     assert hip.hipMemcpy(pos.ctypes.data, d_p, pos.nbytes, 2) == 0
     print(json.dumps({"list": "fuzzed frames", "position_messages_share": round(float(((pos["global_result"] != 0) | (pos["method"] != 0)).mean()), 4),
                       "methods_in_first_block": {str(k): int((pos["method"] == k).sum()) for k in range(5)}}))
     fb = readsb_amd.FIELDS_DTYPE.itemsize
     for name, t, algo in (("k_decode_fields", t_f, n * (64 + fb)), ("k_beast_size+k_beast_write", t_b, n * 64 + nbytes),
-                          ("mgpu_track_gate_device", t_g, n * (64 + fb + 1)), ("mgpu_cpr_track_device", t_c, n * (64 + fb + 32))):
+                          ("mgpu_track_gate_device", t_g, n * (64 + fb + 1)), ("mgpu_cpr_track_device", t_c, n * (64 + fb + 32)),
+                          (f"mgpu_merge_by_time_device (4 segments, {passes} digit passes)", t_m, n * (64 + 64 + 8)),
+                          ("mgpu_beast_encode_ex_device (ids change every message)", t_x, n * (64 + 8) + nbytes_x),
+                          ("k_beast_size+k_beast_write (again, last)", t_b2, n * 64 + nbytes)):
         print(json.dumps({"kernel": name, "messages": n, "ms": round(t * 1e3, 4), "messages_per_s": round(n / t),
                           "algorithmic_GBps": round(algo / t / 1e9, 1), "frac_of_hbm_peak": round(algo / t / 8e12, 4),
                           "timing": "wall clock around the C-ABI call, launch + sync included"}))
