@@ -4,7 +4,7 @@
 //
 // The product has no CPU compute path: without a usable HIP device mgpu_create() fails with
 // MGPU_E_NODEVICE.
-#include "ctx.h"
+#include "behind.h"
 
 // Wait for `pred` (evaluated under c->mu).  During a feed: poll with the lock released and the core offered to others;
 // otherwise block on the condition variable.
@@ -345,6 +345,8 @@ int mgpu_create(const struct mgpu_config *cfg, mgpu_ctx **out) {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device >= ndev) return MGPU_E_NODEVICE;
     mgpu_ctx *c = new (std::nothrow) mgpu_ctx();
     if (!c) return MGPU_E_NOMEM;
+    c->behind.reset(new (std::nothrow) Behind());
+    if (!c->behind) { delete c; return MGPU_E_NOMEM; }
     c->cfg = *cfg;
     if (hipSetDevice(cfg->device) != hipSuccess) { delete c; return MGPU_E_NODEVICE; }
     // the second stream (what follows a chunk's walk; the SC16 formats' float sums) at the lowest priority the device offers: its
@@ -501,10 +503,11 @@ void mgpu_destroy(mgpu_ctx *c) {
     }
     for (hipEvent_t e : c->ev_iq_read)
         if (e) (void) hipEventDestroy(e);
-    void *dev[] = {c->d_merge_scratch, c->d_merge_out, c->d_beast_idw, c->d_beast_ids, c->d_beast_verdict, c->d_cpr_table, c->d_cpr_scratch, c->d_cpr_out, c->d_cpr_cases, c->d_deferred, c->d_gate_table, c->d_gate_scratch, c->d_gate_verdict, c->d_roll_tan, c->d_fields, c->d_beast_off, c->d_beast_len, c->d_beast_in, c->d_beast_out, c->d_beast_blocks, c->d_beast_total, c->d_hist, c->d_hist_iq, c->d_hist_sums, c->d_iq, c->d_win, c->d_adder_bitmap, c->d_bit_syndrome, c->d_group_syndrome, c->d_parity,
+    void *dev[] = {c->d_hist, c->d_hist_iq, c->d_hist_sums, c->d_iq, c->d_win, c->d_adder_bitmap, c->d_bit_syndrome, c->d_group_syndrome, c->d_parity,
                    c->d_tab_long, c->d_tab_short, c->d_uc8_folded};
     for (void *p : dev)
         if (p) (void) hipFree(p);
+    c->behind.reset();                                        // everything behind the message list (behind.h), before its stream goes
     if (c->stream) (void) hipStreamDestroy(c->stream);
     if (c->stream2) (void) hipStreamDestroy(c->stream2);
     if (c->stream_w) (void) hipStreamDestroy(c->stream_w);

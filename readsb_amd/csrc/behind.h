@@ -1,0 +1,49 @@
+// behind.h — private to the library: the device state of what runs behind the message list (behind.cpp).  Only the synchronous calls
+// on stream_aux touch it, never the pipeline's threads.  api.cpp creates it with the context and releases it in mgpu_destroy.
+#pragma once
+#include "ctx.h"
+
+// Owning, grow-only device scratch.  A failed reservation leaves it empty with the context's error text set.
+struct DevBuf {
+    void *p = nullptr;
+    uint64_t cap = 0;                                        // bytes
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release() {
+        if (p) (void) hipFree(p);
+        p = nullptr; cap = 0;
+    }
+    int reserve_exact(mgpu_ctx *c, uint64_t bytes) {
+        if (bytes <= cap) return MGPU_OK;
+        release();
+        HIPCHK(c, hipMalloc(&p, bytes));
+        cap = bytes;
+        return MGPU_OK;
+    }
+    int reserve(mgpu_ctx *c, uint64_t bytes) {               // with slack: lists of slowly growing sizes do not reallocate every call
+        const uint64_t slack = bytes / 4 + 1024;
+        return bytes <= cap ? MGPU_OK : reserve_exact(c, bytes + slack < bytes ? bytes : bytes + slack);
+    }
+    template <class T> T *as() const { return (T *) p; }
+};
+
+struct Behind {
+    // the host-array forms' staged inputs and results: the message list, its verdicts and receiver ids; the beast stream, the deferred list
+    DevBuf d_beast_in, d_beast_verdict, d_beast_ids, d_beast_out, d_deferred;
+    // beast encoder scratch: per message length | signal byte << 8; per workgroup frame bytes | deferred messages and their offsets
+    // (two halves each); the totals {bytes, deferred, last id}; with receiver ids the per-workgroup summaries
+    DevBuf d_beast_len, d_beast_blocks, d_beast_off, d_beast_total, d_beast_idw;
+    DevBuf d_fields;                                         // the host-array forms' field records
+    DevBuf d_roll_tan;                                       // tables.h build_roll_tangent_table(), uploaded on first use
+    // the first-stage tracking gate (kernels/gate.inc): the aircraft table (1 GiB, allocated and zeroed by the first call), its scratch,
+    // the host-array forms' verdicts
+    DevBuf d_gate_table, d_gate_scratch, d_gate_verdict;
+    // CPR pairing + position decode (kernels/cpr.inc): the aircraft table (2 GiB, likewise), its scratch, the host-array forms' positions
+    // and cases | results
+    DevBuf d_cpr_table, d_cpr_scratch, d_cpr_out, d_cpr_cases;
+    // the time merge (kernels/merge.inc): its scratch; the host-array form's merged records | permutation | ids | verdicts
+    DevBuf d_merge_scratch, d_merge_out;
+    int merge_passes = 0;                                    // digit passes of the last merge
+};

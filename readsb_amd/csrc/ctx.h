@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -30,6 +31,8 @@
 #include "tables.h"
 
 using namespace mgpu;
+
+struct Behind;                                                // behind.h
 
 constexpr int kPacketWords = 12;                              // header of a shard packet, 64-bit words: stream position, samples, live records,
 constexpr uint64_t kPacketMagic = 0x3354454b4341504dull;      // magic, candidates, phases 4/5, 6/7, 8 tried, conditional-only / unconditional candidates, buffers, 0
@@ -396,10 +399,6 @@ struct mgpu_ctx {
     uint64_t shard_stream_own_first = 0;
     bool shard_stream = false, shard_stream_cold = false;
     bool shard_marked = false;                                // ... the range has begun for the walker (shard_mark_now): with deferred feeds the walker gets there on its own
-    // beast encoder scratch (mgpu_beast_encode*): grown on demand
-    uint16_t *d_beast_len = nullptr;        // per message: frame length | signal byte << 8
-    uint8_t *d_beast_in = nullptr, *d_beast_out = nullptr;
-    unsigned long long *d_beast_off = nullptr;
     int device_slot = -1;                                     // which of the device's pipeline core groups this context pinned to
     // the ordered walk on the device (kernels/walk.inc).  MGPU_DEVICE_WALK=1: the walker thread only checks the walk's premises
     // and catches the filter up (Resolver::apply_device_walk), the chunk's records stay in HBM; =check: beside the host walk,
@@ -414,30 +413,8 @@ struct mgpu_ctx {
     hipEvent_t ev_wk = nullptr;
     Resolver wk_shadow;                                       // check mode: the state before the host walk, for apply_device_walk
     uint64_t wk_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};          // chunks, taken from the device, not converged, premises failed (host walk), refused, walks, mismatches, -
-    mgpu_fields *d_fields = nullptr;
-    uint64_t fields_cap = 0;
-    double *d_roll_tan = nullptr;                             // tables.h build_roll_tangent_table(), uploaded on first use
-    // the first-stage tracking gate (kernels/gate.inc): the aircraft table (1 GiB, allocated and zeroed by the first call), its scratch
-    void *d_gate_table = nullptr, *d_gate_scratch = nullptr;
-    uint8_t *d_gate_verdict = nullptr;
-    uint64_t gate_cap = 0;
-    // CPR pairing + position decode (kernels/cpr.inc): the aircraft table (2 GiB, allocated and zeroed by the first call), its scratch,
-    // the staged results / cases of the host-array entries
-    void *d_cpr_table = nullptr, *d_cpr_scratch = nullptr, *d_cpr_out = nullptr, *d_cpr_cases = nullptr;
-    uint64_t cpr_cap = 0, cpr_cases_cap = 0;
-    uint32_t *d_beast_blocks = nullptr;
-    mgpu_deferred *d_deferred = nullptr;                      // mgpu_beast_encode_gated's list, device side
-    uint64_t deferred_cap = 0;
     hipStream_t stream_aux = nullptr;                         // field decode / beast encoder / tracking gate: synchronous calls, not behind the pipeline's queued chunks
-    unsigned long long *d_beast_total = nullptr;
-    uint64_t beast_cap_msgs = 0, beast_cap_in = 0, beast_cap_out = 0;
-    // receiver ids in the encoder (mgpu_beast_encode_ex*): the per-workgroup summaries; the host-array form's staged ids and verdicts
-    void *d_beast_idw = nullptr, *d_beast_ids = nullptr, *d_beast_verdict = nullptr;
-    uint64_t beast_cap_idw = 0, beast_cap_ids = 0, beast_cap_verdict = 0;
-    // the time merge (kernels/merge.inc): its scratch; the host-array form's merged records | permutation | ids
-    void *d_merge_scratch = nullptr, *d_merge_out = nullptr;
-    uint64_t merge_cap_scratch = 0, merge_cap_out = 0;
-    int merge_passes = 0;                                     // digit passes of the last merge
+    std::unique_ptr<Behind> behind;                           // ... and their device state (behind.h)
     uint16_t *d_hist = nullptr;                               // magnitudes of the 326 samples before the shard
     uint8_t *d_hist_iq = nullptr;
     unsigned long long *d_hist_sums = nullptr;
