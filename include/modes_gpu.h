@@ -782,6 +782,90 @@ struct mgpu_cpr_result {
 int mgpu_cpr_decode(mgpu_ctx *ctx, const struct mgpu_cpr_case *cases, uint64_t n, struct mgpu_cpr_result *out);
 int mgpu_cpr_decode_device(mgpu_ctx *ctx, const struct mgpu_cpr_case *d_cases, uint64_t n, struct mgpu_cpr_result *d_out);
 
+/* ---- text outputs: BaseStation (SBS) lines and AVR raw lines (kernels/text.inc) ---------------------------------------------------
+ * The two other outputs outputMessage (net_io.c:5822-5885) serves from the point the beast stream leaves at, formatted on the device
+ * from the records the stages above left in HBM.  Streams, offsets and deferred lists work as in mgpu_beast_encode_ex*: the stream of
+ * the lines that are due for certain, in list order; {index, offset its line would start at} for every message whose fate is the host
+ * tracker's, in stream order (*ndeferred counts all of them, the first deferred_cap are written; more than deferred_cap is
+ * MGPU_E_OVERFLOW); MGPU_E_OVERFLOW with *bytes = what the stream needs when it does not fit cap — nothing at or beyond out + cap is
+ * written then (the device form leaves the bytes below cap as they would be, the host form copies nothing).  n == 0 is MGPU_OK.
+ * args->size = sizeof of the caller's struct (MGPU_E_INVAL if smaller than this library's).  Host form: every array in host memory.
+ * _device: msgs, fields, positions, verdict, geom_delta, out and deferred are device pointers; bytes, ndeferred, nskipped are host
+ * pointers in both forms (ndeferred may be NULL without verdicts, nskipped always).  Same stream as the gate and the encoder.
+ *
+ * mgpu_sbs_encode_ex* replaces modesSendSBSOutput (net_io.c:3184-3404, port 30003), fields 1-22 and "\r\n" as at :3249-3401:
+ *   msgType (:3207-3245) from fields.msgtype / metype: DF4/20 5, DF5/21 6, DF0/16 7, DF11 8, DF17/18 by ME type 1-4 1, 5-8 2, 9-18 3,
+ *     19 4; every other DF, Mode A/C and ME types 0 / 20-31: no line.  fields.addr as %06X; bit 24 (MODES_NON_ICAO_ADDRESS): no line (:3191).
+ *   fields 7, 8: msgs[i].sysTimestamp; fields 9, 10: now_ms, ONE value for the whole call (the reference reads the clock per message).
+ *   callsign: fields.callsign up to 8 bytes or its first NUL, iff MGPU_F_CALLSIGN_VALID.  Altitudes and rates as stored, with both
+ *     branches of Modes.use_gnss (MGPU_SBS_USE_GNSS) and their H suffixes (:3275-3293, :3317-3333); the aircraft's geom_delta
+ *     (trackDataValid(&a->geom_delta_valid)) is geom_delta[i], INT32_MIN or a NULL array = not valid; the sums wrap as 32-bit integers.
+ *   gs_selected iff MGPU_F_GS_VALID, heading iff MGPU_F_HEADING_VALID and heading_type == HEADING_GROUND_TRACK (readsb.h:239-242), %.0f.
+ *   position: positions[i].lat / lon as %1.6f iff its method is MGPU_CPR_GLOBAL / _LOCAL_RECEIVER / _LOCAL_AIRCRAFT; a NULL array or any
+ *     other method: ",,".  By design: the reference prints only positions its tracker accepted, so a host tracker vetoes a candidate by
+ *     clearing `method` before the call.
+ *   squawk %04d of fields.squawkDec iff MGPU_F_SQUAWK_VALID; override_squawk != -1 (Modes.sbsOverrideSquawk) wins.  Fields 19-22: alert,
+ *     emergency by the squawk (squawkHex 0x7500 / 0x7600 / 0x7700, :3366-3372), SPI, airground (AG_GROUND "-1", AG_AIRBORNE "0").
+ *   receiverCountMlat, mlatEPU, squawk_emergency_valid and sbs_in are 0 for every demodulated message: those branches do not exist here.
+ *     --sbs-reduce, the sbs_out_mlat / _replay / _jaero / _prio writers and net_forward_min_messages are not modelled.
+ *   Who gets a line (outputMessage calls the writer with an aircraft, :5854, inside its first-message rule, :5846): verdict == NULL:
+ *     every message (a consumer that tracks for itself).  Else with v = verdict[i] (mgpu_track_gate's): due iff (v & 3) == MGPU_GATE_FORWARD
+ *     && (v & MGPU_GATE_AIRCRAFT_CERTAIN); deferred iff MGPU_GATE_AIRCRAFT_POSSIBLE and either (v & 3) == MGPU_GATE_DEFER or FORWARD
+ *     without _CERTAIN; no line otherwise.  A deferred message is listed only if the format has a line for it.
+ *   Domain: a message whose line is due or deferred, but whose sysTimestamp is outside [0, 253402300800000) (years 1970-9999), or whose
+ *     float to be printed is not finite or has |x| >= 2^31, or whose position to be printed is not finite or has |lat| > 90 or |lon| > 360,
+ *     gets no line, no list entry, and adds one to *nskipped: the reference's 200-byte buffer and gmtime_r are undefined there.  A line
+ *     is at most 176 bytes (174 for addresses below 2^25).  now_ms outside the same range is MGPU_E_INVAL.
+ *   fields == NULL, host form only: the library decodes the fields itself, as mgpu_track_gate does; _device: MGPU_E_INVAL.
+ *   The printf conversions are reproduced exactly, in integer arithmetic: %1.6f and %.0f round the binary value half to even.
+ *
+ * mgpu_raw_encode_ex* replaces modesSendRawOutput (net_io.c:1837-1863, port 30002): '*', or '@' and 12 hex digits iff MGPU_RAW_MLAT
+ *   (Modes.mlat) and timestamp != 0; msgbits / 8 bytes as uppercase hex pairs; ";\n".  The 12 digits are the 12 MOST significant hex
+ *   digits of the timestamp as uint64 zero-padded to 12 — what sprintf("@%012" PRIX64) followed by p += 13 leaves (:1848-1850); below
+ *   2^48 simply the value.  Only msgbits 16, 56, 112 get a line.  MGPU_RAW_VERBATIM (--net-verbatim): raw[] for msg[], both forwarding
+ *   tests lifted, nothing deferred.  MGPU_RAW_NET_RULE: also correctedbits < 2 (:5863).  verdict: MGPU_GATE_FORWARD a line,
+ *   MGPU_GATE_DEFER listed, NULL every message (the raw writer needs no aircraft): mgpu_beast_encode_ex's rules without ids. */
+#define MGPU_SBS_USE_GNSS  1u
+struct mgpu_sbs_args {
+    uint32_t size;                     /* sizeof(struct mgpu_sbs_args) */
+    uint32_t flags;                    /* MGPU_SBS_USE_GNSS */
+    const struct mgpu_msg *msgs;
+    const struct mgpu_fields *fields;  /* [n]; NULL (host form): decoded by the library */
+    const struct mgpu_position *positions;   /* [n] or NULL */
+    const uint8_t *verdict;            /* [n] or NULL */
+    const int32_t *geom_delta;         /* [n] or NULL */
+    uint64_t n;
+    int64_t now_ms;
+    int32_t override_squawk;           /* -1: none */
+    uint8_t *out;
+    uint64_t cap;
+    uint64_t *bytes;                   /* host, out */
+    struct mgpu_deferred *deferred;    /* [deferred_cap] or NULL */
+    uint64_t deferred_cap;
+    uint64_t *ndeferred, *nskipped;    /* host, out; may be NULL (ndeferred: without verdicts) */
+};
+int mgpu_sbs_encode_ex(mgpu_ctx *ctx, const struct mgpu_sbs_args *args);
+int mgpu_sbs_encode_ex_device(mgpu_ctx *ctx, const struct mgpu_sbs_args *args);
+
+#define MGPU_RAW_NET_RULE  1u
+#define MGPU_RAW_VERBATIM  2u
+#define MGPU_RAW_MLAT      4u
+struct mgpu_raw_args {
+    uint32_t size;                     /* sizeof(struct mgpu_raw_args) */
+    uint32_t flags;                    /* MGPU_RAW_* */
+    const struct mgpu_msg *msgs;
+    const uint8_t *verdict;            /* [n] or NULL */
+    uint64_t n;
+    uint8_t *out;
+    uint64_t cap;
+    uint64_t *bytes;                   /* host, out */
+    struct mgpu_deferred *deferred;    /* [deferred_cap] or NULL */
+    uint64_t deferred_cap;
+    uint64_t *ndeferred;               /* host, out; may be NULL without verdicts */
+};
+int mgpu_raw_encode_ex(mgpu_ctx *ctx, const struct mgpu_raw_args *args);
+int mgpu_raw_encode_ex_device(mgpu_ctx *ctx, const struct mgpu_raw_args *args);
+
 /* ---- tables, for known-answer tests against crc.c --------------------------------- */
 
 /* These run on the host (they are how the device tables are built) and need no context. */

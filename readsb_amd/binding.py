@@ -156,6 +156,26 @@ class BeastArgs(C.Structure):                                         # struct m
                 ("ids", C.c_void_p), ("last_id", C.POINTER(C.c_uint64)), ("out", C.c_void_p), ("cap", C.c_uint64),
                 ("bytes", C.POINTER(C.c_uint64)), ("deferred", C.c_void_p), ("deferred_cap", C.c_uint64),
                 ("ndeferred", C.POINTER(C.c_uint64))]
+
+
+SBS_USE_GNSS = 1                                                      # MGPU_SBS_*
+RAW_NET_RULE, RAW_VERBATIM, RAW_MLAT = 1, 2, 4                        # MGPU_RAW_*
+SBS_LINE_MAX, RAW_LINE_MAX = 176, 43                                  # bytes of a line
+
+
+class SbsArgs(C.Structure):                                           # struct mgpu_sbs_args
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("msgs", C.c_void_p), ("fields", C.c_void_p), ("positions", C.c_void_p),
+                ("verdict", C.c_void_p), ("geom_delta", C.c_void_p), ("n", C.c_uint64), ("now_ms", C.c_int64), ("override_squawk", C.c_int32),
+                ("out", C.c_void_p), ("cap", C.c_uint64), ("bytes", C.POINTER(C.c_uint64)), ("deferred", C.c_void_p),
+                ("deferred_cap", C.c_uint64), ("ndeferred", C.POINTER(C.c_uint64)), ("nskipped", C.POINTER(C.c_uint64))]
+
+
+class RawArgs(C.Structure):                                           # struct mgpu_raw_args
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("msgs", C.c_void_p), ("verdict", C.c_void_p), ("n", C.c_uint64),
+                ("out", C.c_void_p), ("cap", C.c_uint64), ("bytes", C.POINTER(C.c_uint64)), ("deferred", C.c_void_p),
+                ("deferred_cap", C.c_uint64), ("ndeferred", C.POINTER(C.c_uint64))]
+
+
 ABI_VERSION = 6                             # MGPU_ABI_VERSION of the include/modes_gpu.h these ctypes mirrors were written against
 
 
@@ -329,6 +349,10 @@ def load_library():
     lib.mgpu_beast_encode_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
     lib.mgpu_beast_encode_ex.argtypes = [vp, C.POINTER(BeastArgs)]
     lib.mgpu_beast_encode_ex_device.argtypes = [vp, C.POINTER(BeastArgs)]
+    lib.mgpu_sbs_encode_ex.argtypes = [vp, C.POINTER(SbsArgs)]
+    lib.mgpu_sbs_encode_ex_device.argtypes = [vp, C.POINTER(SbsArgs)]
+    lib.mgpu_raw_encode_ex.argtypes = [vp, C.POINTER(RawArgs)]
+    lib.mgpu_raw_encode_ex_device.argtypes = [vp, C.POINTER(RawArgs)]
     lib.mgpu_merge_by_time.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
     lib.mgpu_merge_by_time_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
     lib.mgpu_merge_last_passes.argtypes = [vp]
@@ -716,6 +740,76 @@ class Demodulator:
                       C.pointer(nb), d_deferred_ptr, deferred_cap, C.pointer(nd))
         self._chk(self.lib.mgpu_beast_encode_ex_device(self.ctx, C.byref(a)), "mgpu_beast_encode_ex_device")
         return int(nb.value), int(nd.value), int(last.value)
+
+    def sbs_encode(self, msgs, now_ms, fields=None, positions=None, verdict=None, geom_delta=None, use_gnss=False, override_squawk=-1, deferred_cap=None):
+        """mgpu_sbs_encode_ex on host arrays: the BaseStation lines of a record array (include/modes_gpu.h).  fields: decode_fields'
+        records or None (decoded by the library); positions: cpr_track's records or None; verdict: the gate's bytes or None (every
+        message has an aircraft); geom_delta: one int32 per message, INT32_MIN = not valid.  -> (stream bytes, deferred[] records,
+        the number of messages outside the printable domain)."""
+        msgs = np.ascontiguousarray(msgs)
+        assert msgs.dtype == MSG_DTYPE
+        n = len(msgs)
+
+        def arr(a, dtype):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            assert len(a) == n
+            return a
+        fields, positions = arr(fields, FIELDS_DTYPE), arr(positions, POSITION_DTYPE)
+        verdict, geom_delta = arr(verdict, np.uint8), arr(geom_delta, np.int32)
+        cap = n * SBS_LINE_MAX + 64
+        out = np.empty(cap, dtype=np.uint8)
+        dcap = int(deferred_cap if deferred_cap is not None else (n if verdict is not None else 0))
+        deferred = np.zeros(max(dcap, 1), dtype=DEFERRED_DTYPE)
+        nb, nd, ns = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        ptr = lambda a: a.ctypes.data if a is not None else None                                     # noqa: E731
+        a = SbsArgs(C.sizeof(SbsArgs), SBS_USE_GNSS if use_gnss else 0, msgs.ctypes.data, ptr(fields), ptr(positions), ptr(verdict), ptr(geom_delta),
+                    n, int(now_ms), int(override_squawk), out.ctypes.data, cap, C.pointer(nb), deferred.ctypes.data, dcap, C.pointer(nd), C.pointer(ns))
+        self._chk(self.lib.mgpu_sbs_encode_ex(self.ctx, C.byref(a)), "mgpu_sbs_encode_ex")
+        return out[: nb.value].tobytes(), deferred[: nd.value].copy(), int(ns.value)
+
+    def sbs_encode_device(self, d_msgs_ptr, d_fields_ptr, n, now_ms, d_out_ptr, cap, d_positions_ptr=None, d_verdict_ptr=None, d_geom_delta_ptr=None,
+                          use_gnss=False, override_squawk=-1, d_deferred_ptr=None, deferred_cap=0):
+        """mgpu_sbs_encode_ex_device: everything in HBM (pointers as ints).  -> (the stream's size in bytes, the number of deferred
+        messages, the number of skipped messages)."""
+        nb, nd, ns = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        a = SbsArgs(C.sizeof(SbsArgs), SBS_USE_GNSS if use_gnss else 0, d_msgs_ptr, d_fields_ptr, d_positions_ptr, d_verdict_ptr, d_geom_delta_ptr,
+                    n, int(now_ms), int(override_squawk), d_out_ptr, cap, C.pointer(nb), d_deferred_ptr, deferred_cap, C.pointer(nd), C.pointer(ns))
+        self._chk(self.lib.mgpu_sbs_encode_ex_device(self.ctx, C.byref(a)), "mgpu_sbs_encode_ex_device")
+        return int(nb.value), int(nd.value), int(ns.value)
+
+    @staticmethod
+    def _raw_flags(mlat, net_rule, verbatim):
+        return (RAW_MLAT if mlat else 0) | (RAW_NET_RULE if net_rule else 0) | (RAW_VERBATIM if verbatim else 0)
+
+    def raw_encode(self, msgs, mlat=False, verdict=None, net_rule=False, verbatim=False, deferred_cap=None):
+        """mgpu_raw_encode_ex on host arrays: the AVR raw lines ('*...;' or, with mlat, '@' + 12 timestamp digits) of a record array.
+        verdict / net_rule / verbatim as in beast_encode_ex.  -> (stream bytes, deferred[] records)."""
+        msgs = np.ascontiguousarray(msgs)
+        assert msgs.dtype == MSG_DTYPE
+        n = len(msgs)
+        if verdict is not None:
+            verdict = np.ascontiguousarray(verdict, dtype=np.uint8)
+            assert len(verdict) == n
+        cap = n * RAW_LINE_MAX + 64
+        out = np.empty(cap, dtype=np.uint8)
+        dcap = int(deferred_cap if deferred_cap is not None else (n if verdict is not None else 0))
+        deferred = np.zeros(max(dcap, 1), dtype=DEFERRED_DTYPE)
+        nb, nd = C.c_uint64(0), C.c_uint64(0)
+        a = RawArgs(C.sizeof(RawArgs), self._raw_flags(mlat, net_rule, verbatim), msgs.ctypes.data, verdict.ctypes.data if verdict is not None else None,
+                    n, out.ctypes.data, cap, C.pointer(nb), deferred.ctypes.data, dcap, C.pointer(nd))
+        self._chk(self.lib.mgpu_raw_encode_ex(self.ctx, C.byref(a)), "mgpu_raw_encode_ex")
+        return out[: nb.value].tobytes(), deferred[: nd.value].copy()
+
+    def raw_encode_device(self, d_msgs_ptr, n, d_out_ptr, cap, mlat=False, d_verdict_ptr=None, net_rule=False, verbatim=False, d_deferred_ptr=None,
+                          deferred_cap=0):
+        """mgpu_raw_encode_ex_device: everything in HBM (pointers as ints).  -> (the stream's size in bytes, the number of deferred messages)."""
+        nb, nd = C.c_uint64(0), C.c_uint64(0)
+        a = RawArgs(C.sizeof(RawArgs), self._raw_flags(mlat, net_rule, verbatim), d_msgs_ptr, d_verdict_ptr, n, d_out_ptr, cap, C.pointer(nb),
+                    d_deferred_ptr, deferred_cap, C.pointer(nd))
+        self._chk(self.lib.mgpu_raw_encode_ex_device(self.ctx, C.byref(a)), "mgpu_raw_encode_ex_device")
+        return int(nb.value), int(nd.value)
 
     def merge_by_time(self, lists, ids=None, verdicts=None):
         """mgpu_merge_by_time on host arrays: the receivers' lists merged by timestamp on the GPU, equal stamps in input order —

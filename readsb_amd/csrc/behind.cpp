@@ -1,4 +1,4 @@
-// behind.cpp — behind the message list: beast encoder, field decode, tracking gate, position decode, and the CRC / table diagnostics.
+// behind.cpp — behind the message list: beast encoder, field decode, tracking gate, position decode, the text outputs, and the CRC / table diagnostics.
 #include "behind.h"
 
 #include <cmath>
@@ -407,6 +407,165 @@ int mgpu_cpr_decode(mgpu_ctx *c, const struct mgpu_cpr_case *cases, uint64_t n, 
     HIPCHK(c, hipMemcpyAsync(out, d_out, n * sizeof(mgpu_cpr_result), hipMemcpyDeviceToHost, c->stream_aux));
     HIPCHK(c, hipStreamSynchronize(c->stream_aux));
     return MGPU_OK;
+}
+
+// ---- text outputs: SBS lines (modesSendSBSOutput, net_io.c:3184-3404) and AVR raw lines (modesSendRawOutput, net_io.c:1837-1863), kernels/text.inc ----
+
+static int text_scratch(mgpu_ctx *c, uint64_t n, TextScratch *w) {
+    Behind &b = *c->behind;
+    const size_t nb = (size_t) (n / kBlock + 2);                 // per workgroup: bytes | deferred | skipped, nb entries each
+    if (int rc = b.d_text_len.reserve(c, n * sizeof(uint16_t))) return rc;
+    if (int rc = b.d_text_blocks.reserve(c, 3 * nb * sizeof(uint32_t))) return rc;
+    if (int rc = b.d_text_off.reserve(c, 3 * nb * sizeof(unsigned long long))) return rc;
+    if (int rc = b.d_text_total.reserve_exact(c, 4 * sizeof(unsigned long long))) return rc;
+    *w = {b.d_text_len.as<uint16_t>(), b.d_text_blocks.as<uint32_t>(), b.d_text_off.as<unsigned long long>(), b.d_text_total.as<unsigned long long>(), nb};
+    return MGPU_OK;
+}
+
+// behind either launch: the three totals back, the caller's counts, the overflow answers
+static int text_finish(mgpu_ctx *c, const TextScratch &w, bool gated, uint64_t cap, uint64_t deferred_cap, uint64_t *bytes, uint64_t *ndeferred,
+                       uint64_t *nskipped, bool skips) {
+    HIPCHK(c, hipGetLastError());
+    unsigned long long total[3] = {0, 0, 0};                     // (the third is computed only for a job that can skip: SBS)
+    HIPCHK(c, hipMemcpyAsync(total, w.total, (skips ? 3 : 2) * sizeof total[0], hipMemcpyDeviceToHost, c->stream_aux));
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    *bytes = total[0];
+    if (ndeferred) *ndeferred = gated ? total[1] : 0;
+    if (nskipped) *nskipped = total[2];
+    if (total[0] > cap) { c->err = "text encode: output buffer too small"; return MGPU_E_OVERFLOW; }
+    if (gated && total[1] > deferred_cap) { c->err = "text encode: more deferred messages than the list holds"; return MGPU_E_OVERFLOW; }
+    return MGPU_OK;
+}
+
+// a: every array a device pointer
+static int sbs_encode_dev(mgpu_ctx *c, const struct mgpu_sbs_args &a) {
+    TextScratch w;
+    if (int rc = text_scratch(c, a.n, &w)) return rc;
+    const TextSbsParams p = {a.msgs, a.fields, a.positions, a.verdict, a.geom_delta, a.now_ms, a.override_squawk, a.flags};
+    launch_sbs_encode(p, a.n, w, a.out, a.cap, a.deferred, a.verdict ? a.deferred_cap : 0, c->stream_aux);
+    return text_finish(c, w, a.verdict != nullptr, a.cap, a.deferred_cap, a.bytes, a.ndeferred, a.nskipped, true);
+}
+
+static int raw_encode_dev(mgpu_ctx *c, const struct mgpu_raw_args &a) {
+    TextScratch w;
+    if (int rc = text_scratch(c, a.n, &w)) return rc;
+    const bool gated = a.verdict && !(a.flags & MGPU_RAW_VERBATIM);
+    const TextRawParams p = {a.msgs, gated ? a.verdict : nullptr, a.flags};
+    launch_raw_encode(p, a.n, w, a.out, a.cap, a.deferred, gated ? a.deferred_cap : 0, c->stream_aux);
+    return text_finish(c, w, gated, a.cap, a.deferred_cap, a.bytes, a.ndeferred, nullptr, false);
+}
+
+static bool sbs_args_ok(const struct mgpu_sbs_args *a, bool device) {
+    if (!a || a->size < sizeof(struct mgpu_sbs_args) || !a->bytes) return false;
+    if (a->flags & ~MGPU_SBS_USE_GNSS) return false;
+    if (a->now_ms < 0 || a->now_ms >= 253402300800000ll) return false;       // years 1970-9999, as for every sysTimestamp
+    if (a->n && (!a->msgs || !a->out || (device && !a->fields))) return false;
+    if (a->verdict && (!a->ndeferred || (a->deferred_cap && !a->deferred))) return false;
+    return true;
+}
+
+static bool raw_args_ok(const struct mgpu_raw_args *a) {
+    if (!a || a->size < sizeof(struct mgpu_raw_args) || !a->bytes) return false;
+    if (a->flags & ~(MGPU_RAW_NET_RULE | MGPU_RAW_VERBATIM | MGPU_RAW_MLAT)) return false;
+    if (a->n && (!a->msgs || !a->out)) return false;
+    const bool gated = a->verdict && !(a->flags & MGPU_RAW_VERBATIM);
+    if (gated && (!a->ndeferred || (a->deferred_cap && !a->deferred))) return false;
+    return true;
+}
+
+// the staged outputs of a host-array form: room for them before the launch, the stream and the listed entries back after it
+static int text_out_reserve(mgpu_ctx *c, uint64_t cap, bool gated, uint64_t deferred_cap) {
+    Behind &b = *c->behind;
+    if (int rc = b.d_beast_out.reserve(c, cap + 64)) return rc;
+    if (gated)
+        if (int rc = b.d_deferred.reserve(c, (deferred_cap + 64) * sizeof(mgpu_deferred))) return rc;
+    return MGPU_OK;
+}
+static int text_out_fetch(mgpu_ctx *c, uint8_t *out, uint64_t bytes, struct mgpu_deferred *deferred, const uint64_t *ndeferred) {
+    Behind &b = *c->behind;
+    if (bytes) HIPCHK(c, hipMemcpy(out, b.d_beast_out.p, bytes, hipMemcpyDeviceToHost));
+    if (ndeferred && *ndeferred) HIPCHK(c, hipMemcpy(deferred, b.d_deferred.p, *ndeferred * sizeof(mgpu_deferred), hipMemcpyDeviceToHost));
+    return MGPU_OK;
+}
+
+int mgpu_sbs_encode_ex_device(mgpu_ctx *c, const struct mgpu_sbs_args *a) {
+    if (!c || !sbs_args_ok(a, true)) return MGPU_E_INVAL;
+    *a->bytes = 0;
+    if (a->ndeferred) *a->ndeferred = 0;
+    if (a->nskipped) *a->nskipped = 0;
+    if (a->n == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return sbs_encode_dev(c, *a);
+}
+
+int mgpu_sbs_encode_ex(mgpu_ctx *c, const struct mgpu_sbs_args *a) {
+    if (!c || !sbs_args_ok(a, false)) return MGPU_E_INVAL;
+    *a->bytes = 0;
+    if (a->ndeferred) *a->ndeferred = 0;
+    if (a->nskipped) *a->nskipped = 0;
+    const uint64_t n = a->n;
+    if (n == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    Behind &b = *c->behind;
+    struct mgpu_sbs_args d = *a;
+    if (a->fields) {
+        if (int rc = stage_messages(c, a->msgs, n, a->verdict)) return rc;
+        if (int rc = b.d_fields.reserve(c, n * sizeof(mgpu_fields))) return rc;
+        HIPCHK(c, hipMemcpyAsync(b.d_fields.p, a->fields, n * sizeof(mgpu_fields), hipMemcpyHostToDevice, c->stream_aux));
+    } else {
+        if (int rc = fields_staged(c, a->msgs, n)) return rc;
+        if (a->verdict) {
+            if (int rc = b.d_beast_verdict.reserve(c, n)) return rc;
+            HIPCHK(c, hipMemcpyAsync(b.d_beast_verdict.p, a->verdict, n, hipMemcpyHostToDevice, c->stream_aux));
+        }
+    }
+    d.msgs = b.d_beast_in.as<mgpu_msg>();
+    d.fields = b.d_fields.as<mgpu_fields>();
+    if (a->verdict) d.verdict = b.d_beast_verdict.as<uint8_t>();
+    if (a->positions) {
+        if (int rc = b.d_text_pos.reserve(c, n * sizeof(mgpu_position))) return rc;
+        HIPCHK(c, hipMemcpyAsync(b.d_text_pos.p, a->positions, n * sizeof(mgpu_position), hipMemcpyHostToDevice, c->stream_aux));
+        d.positions = b.d_text_pos.as<mgpu_position>();
+    }
+    if (a->geom_delta) {
+        if (int rc = b.d_text_delta.reserve(c, n * sizeof(int32_t))) return rc;
+        HIPCHK(c, hipMemcpyAsync(b.d_text_delta.p, a->geom_delta, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream_aux));
+        d.geom_delta = b.d_text_delta.as<int32_t>();
+    }
+    if (int rc = text_out_reserve(c, a->cap, a->verdict != nullptr, a->deferred_cap)) return rc;
+    d.out = b.d_beast_out.as<uint8_t>();
+    d.deferred = b.d_deferred.as<mgpu_deferred>();
+    if (int rc = sbs_encode_dev(c, d)) return rc;
+    return text_out_fetch(c, a->out, *a->bytes, a->deferred, a->verdict ? a->ndeferred : nullptr);
+}
+
+int mgpu_raw_encode_ex_device(mgpu_ctx *c, const struct mgpu_raw_args *a) {
+    if (!c || !raw_args_ok(a)) return MGPU_E_INVAL;
+    *a->bytes = 0;
+    if (a->ndeferred) *a->ndeferred = 0;
+    if (a->n == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return raw_encode_dev(c, *a);
+}
+
+int mgpu_raw_encode_ex(mgpu_ctx *c, const struct mgpu_raw_args *a) {
+    if (!c || !raw_args_ok(a)) return MGPU_E_INVAL;
+    *a->bytes = 0;
+    if (a->ndeferred) *a->ndeferred = 0;
+    const uint64_t n = a->n;
+    if (n == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    Behind &b = *c->behind;
+    const bool gated = a->verdict && !(a->flags & MGPU_RAW_VERBATIM);
+    if (int rc = stage_messages(c, a->msgs, n, gated ? a->verdict : nullptr)) return rc;
+    if (int rc = text_out_reserve(c, a->cap, gated, a->deferred_cap)) return rc;
+    struct mgpu_raw_args d = *a;
+    d.msgs = b.d_beast_in.as<mgpu_msg>();
+    d.verdict = gated ? b.d_beast_verdict.as<uint8_t>() : nullptr;
+    d.out = b.d_beast_out.as<uint8_t>();
+    d.deferred = b.d_deferred.as<mgpu_deferred>();
+    if (int rc = raw_encode_dev(c, d)) return rc;
+    return text_out_fetch(c, a->out, *a->bytes, a->deferred, gated ? a->ndeferred : nullptr);
 }
 
 uint32_t mgpu_crc_checksum(const uint8_t *msg, int bits) { return crc_tables().checksum(msg, bits); }

@@ -209,6 +209,32 @@ void launch_beast_encode(const mgpu_msg *msgs, uint64_t n, uint16_t *meta, uint3
                          int verbatim = 0, const unsigned long long *ids = nullptr /* per message: total[2] = the last caller's */,
                          unsigned long long last_id = 0, void *id_scratch = nullptr /* beast_id_scratch_bytes(n), with ids */);
 size_t beast_id_scratch_bytes(uint64_t n);
+// the text outputs (kernels/text.inc): SBS lines (modesSendSBSOutput, net_io.c:3184-3404) and AVR raw lines (modesSendRawOutput,
+// net_io.c:1837-1863) of n records in device memory.  Everything a job reads is a device pointer; null where modes_gpu.h allows it.
+struct TextSbsParams {
+    const mgpu_msg *msgs;
+    const mgpu_fields *fields;
+    const mgpu_position *positions;
+    const uint8_t *verdict;
+    const int32_t *geom_delta;
+    int64_t now_ms;
+    int32_t override_squawk;
+    uint32_t flags;                   // MGPU_SBS_*
+};
+struct TextRawParams {
+    const mgpu_msg *msgs;
+    const uint8_t *verdict;
+    uint32_t flags;                   // MGPU_RAW_*
+};
+struct TextScratch {
+    uint16_t *meta;                   // [n] a line's length, or the deferred mark
+    uint32_t *blocks;                 // [3 * stride] per workgroup: bytes | deferred messages | skipped messages
+    unsigned long long *off;          // [3 * stride] the exclusive prefix sums of the first two
+    unsigned long long *total;        // [3] the totals (skipped: SBS only)
+    size_t stride;                    // >= ceil(n / kBlock)
+};
+void launch_sbs_encode(const TextSbsParams &a, uint64_t n, const TextScratch &w, uint8_t *out, uint64_t cap, mgpu_deferred *deferred, uint64_t def_cap, hipStream_t s);
+void launch_raw_encode(const TextRawParams &a, uint64_t n, const TextScratch &w, uint8_t *out, uint64_t cap, mgpu_deferred *deferred, uint64_t def_cap, hipStream_t s);
 // stable merge of message lists by timestamp (kernels/merge.inc): segs [nseg] in device memory, scratch = merge_scratch_bytes(n, nseg)
 struct MergeSeg {
     const mgpu_msg *msgs;

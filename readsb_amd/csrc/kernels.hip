@@ -11,6 +11,7 @@
 //   k_window_stats   what the skip-ahead hid from the counters (demod_2400.c:468)
 //   k_modeac*, k_beast_*, k_decode_fields: Mode A/C demodulator, beast wire encoder, per-message field decode
 //   k_gate_*, k_cpr_*  first stage of the tracker, CPR pairing and position decode over the message list (track.c, cpr.c)
+//   k_text_*         SBS and AVR raw text lines of the message list (net_io.c:3184-3404, 1837-1863)
 //
 // No MFMA anywhere: this is HBM-bound integer/byte streaming work.  All arithmetic on the
 // message path is integer and bit-exact with the reference; the SC16 converters use IEEE float
@@ -121,6 +122,7 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 #include "kernels/walk.inc"      // the ordered walk on the device: experiments build only (the host owns the walk)
 #endif
 #include "kernels/beast.inc"
+#include "kernels/text.inc"
 #include "kernels/fields.inc"
 #include "kernels/gate.inc"
 #include "kernels/merge.inc"

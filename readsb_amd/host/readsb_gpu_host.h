@@ -81,6 +81,12 @@ int gpu_ifile_run(struct gpu_demod *g, int fd, input_format_t format, unsigned c
 /* the same with the reader loop's exit flag (Modes.exit, sdr_ifile.c:197) and a running sample count; both may be NULL */
 int gpu_ifile_run_until(struct gpu_demod *g, int fd, input_format_t format, unsigned chunk_buffers, const volatile int *stop, uint64_t *samples);
 
+/* readsb_gpu_ifile --sbs-out (sbs_gpu.c): every chunk of the file a deferred feed whose records stay in HBM, then field decode, tracking
+ * gate, position decode and mgpu_sbs_encode_ex_device on them; only the lines come back and go to `path`.  Messages the gate defers
+ * to a position tracker are dropped.  now_ms: fields 9 and 10.  counters: the demodulator's, at the end. */
+struct gpu_sbs_opts { const char *path; int64_t now_ms; int have_ref, gnss; double lat, lon; };
+int gpu_sbs_run(mgpu_ctx *ctx, int fd, input_format_t format, unsigned chunk_buffers, const struct gpu_sbs_opts *o, struct mgpu_counters *counters);
+
 /* ---- fan-in: many sample streams, one demodulator context each -------------------------------
  * The aggregator's input side (README.md:40-51: several receivers feeding one readsb): an sdr_handler-shaped row
  * (sdr.c:94-122: initConfig / handleOption / open / run / cancel / close) that takes any number of `--ifile`s.  Every

@@ -2,6 +2,8 @@
  * with the demodulator on the GPU: prints one `@<12-hex 12 MHz timestamp><frame hex>;` line per
  * accepted message exactly as displayModesMessage does in --raw --mlat mode (mode_s.c:1834-1847),
  * and with --stats the demodulator counters of display_stats (stats.c:65-125).
+ * --sbs-out PATH: instead of the raw lines, the BaseStation feed of the capture (modesSendSBSOutput, net_io.c:3184-3404) into PATH,
+ * with nothing but the text leaving the GPU: feed -> field decode -> tracking gate -> position decode -> SBS encoder (sbs_gpu.c).
  */
 #include <fcntl.h>
 #include <inttypes.h>
@@ -10,6 +12,8 @@
 #include <string.h>
 #include <strings.h>
 #include <unistd.h>
+
+#include <time.h>
 
 #include "readsb_gpu_host.h"
 
@@ -25,6 +29,22 @@ static void print_raw_line(FILE *out, const struct gpu_modes_message *mm) {
 
 static void print_raw(const struct gpu_modes_message *mm, void *user) { print_raw_line(user, mm); }
 
+static const char usage[] =
+    "readsb_gpu_ifile --ifile PATH|- [--iformat UC8|SC16|SC16Q11] [--fix|--no-fix|--aggressive] [--no-fix-df] [--modeac]\n"
+    "                 [--preamble-threshold N] [--gpu-device N] [--gpu-chunk-buffers N] [--startup-time-ms MS] [--stats] [--raw --mlat]\n"
+    "                 [--sbs-out PATH [--sbs-now-ms MS] [--lat DEG --lon DEG] [--gnss]]\n"
+    "  default: one `@<timestamp><frame>;` line per accepted message on stdout (readsb --raw --mlat)\n"
+    "  --sbs-out PATH   write the BaseStation (port 30003) lines of the capture to PATH instead; the messages, their field records,\n"
+    "                   the tracking gate's verdicts and the decoded positions stay on the GPU, only the text comes back.\n"
+    "                   Messages whose forwarding is the position tracker's decision (deferred by the gate) are DROPPED, as\n"
+    "                   readsb_gpu_gather --forward-only drops them; their number is reported on stderr.  Not with --modeac.\n"
+    "  --sbs-now-ms MS  the time printed in fields 9 and 10 (ms since 1970; default: the clock when the program starts)\n"
+    "  --lat, --lon     the receiver's location (enables positions relative to the receiver and surface positions)\n"
+    "  --gnss           Modes.use_gnss: geometric altitudes and rates with the H suffix where available\n";
+
+/* readsb_amd/host/sbs_gpu.c; absent from builds against a stand-in library, which have no device to keep anything on */
+#pragma weak gpu_sbs_run
+
 int main(int argc, char **argv) {
     struct mgpu_config cfg;
     mgpu_config_defaults(&cfg);
@@ -32,6 +52,8 @@ int main(int argc, char **argv) {
     input_format_t fmt = INPUT_UC8;
     int stats = 0;
     unsigned chunk = 256;
+    struct gpu_sbs_opts sbs = {NULL, -1, 0, 0, 0.0, 0.0};
+    int have_lat = 0, have_lon = 0;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--ifile") && i + 1 < argc) ifile = argv[++i];
         else if (!strcmp(argv[i], "--iformat") && i + 1 < argc) {
@@ -47,9 +69,23 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--gpu-chunk-buffers") && i + 1 < argc) chunk = (unsigned) atoi(argv[++i]);
         else if (!strcmp(argv[i], "--startup-time-ms") && i + 1 < argc) cfg.startup_time_ms = atoll(argv[++i]);
         else if (!strcmp(argv[i], "--stats")) stats = 1;
+        else if (!strcmp(argv[i], "--sbs-out") && i + 1 < argc) sbs.path = argv[++i];
+        else if (!strcmp(argv[i], "--sbs-now-ms") && i + 1 < argc) sbs.now_ms = atoll(argv[++i]);
+        else if (!strcmp(argv[i], "--lat") && i + 1 < argc) { sbs.lat = atof(argv[++i]); have_lat = 1; }
+        else if (!strcmp(argv[i], "--lon") && i + 1 < argc) { sbs.lon = atof(argv[++i]); have_lon = 1; }
+        else if (!strcmp(argv[i], "--gnss")) sbs.gnss = 1;
+        else if (!strcmp(argv[i], "--help")) { fputs(usage, stdout); return 0; }
         else if (!strcmp(argv[i], "--raw") || !strcmp(argv[i], "--mlat") || !strcmp(argv[i], "--quiet")) { }
         else if (!strcmp(argv[i], "--device-type") && i + 1 < argc) ++i;
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
+    }
+    sbs.have_ref = have_lat && have_lon;
+    if (sbs.path && !gpu_sbs_run) { fprintf(stderr, "--sbs-out: this build has no GPU chain\n"); return 2; }
+    if (sbs.path && cfg.mode_ac) { fprintf(stderr, "--sbs-out: not with --modeac (its replies are merged on the host)\n"); return 2; }
+    if (sbs.path && sbs.now_ms < 0) {
+        struct timespec ts;
+        clock_gettime(CLOCK_REALTIME, &ts);
+        sbs.now_ms = (int64_t) ts.tv_sec * 1000 + ts.tv_nsec / 1000000;
     }
     if (!ifile) { fprintf(stderr, "SDR type 'ifile' requires an --ifile argument\n"); return 2; }   /* sdr_ifile.c:118 */
     int fd = !strcmp(ifile, "-") ? STDIN_FILENO : open(ifile, O_RDONLY);
@@ -58,8 +94,8 @@ int main(int argc, char **argv) {
     cfg.max_samples = (uint64_t) chunk * 131072;
     struct gpu_demod g;
     if (gpu_demod_open(&g, &cfg, print_raw, stdout) != MGPU_OK) return 1;
-    int rc = gpu_ifile_run(&g, fd, fmt, chunk);
-    if (rc != MGPU_OK) fprintf(stderr, "gpu_ifile_run: %s (%s)\n", mgpu_strerror(rc), mgpu_last_error(g.ctx));
+    int rc = sbs.path ? gpu_sbs_run(g.ctx, fd, fmt, chunk, &sbs, &g.counters) : gpu_ifile_run(&g, fd, fmt, chunk);
+    if (rc != MGPU_OK && !sbs.path) fprintf(stderr, "gpu_ifile_run: %s (%s)\n", mgpu_strerror(rc), mgpu_last_error(g.ctx));
     fflush(stdout);
     if (stats && rc == MGPU_OK) {
         const struct mgpu_counters *c = &g.counters;
