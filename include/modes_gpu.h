@@ -866,6 +866,79 @@ struct mgpu_raw_args {
 int mgpu_raw_encode_ex(mgpu_ctx *ctx, const struct mgpu_raw_args *args);
 int mgpu_raw_encode_ex_device(mgpu_ctx *ctx, const struct mgpu_raw_args *args);
 
+/* ---- ASTERIX CAT021 target reports (kernels/asterix.inc) ------------------------------------------------------------------------------
+ * mgpu_asterix_encode_ex* replaces modesSendAsterixOutput (net_io.c:2416-2945, --net-asterix-out-port / the asterix_out connector), the
+ * fourth writer outputMessage serves, over the same records and with the stream, offset, deferred-list, overflow, n == 0, size and stream
+ * rules of mgpu_sbs_encode_ex* above.  A record: the category byte 21, a 16-bit big-endian length, an FSPEC of 4 to 6 bytes with the
+ * extension bits set from the back (:2920-2927), the items in the order the reference appends them (NOT the order of the UAP).  The
+ * writer is mirrored operation for operation; what looks like a mistake in it is kept:
+ *   I021/010 SAC 0, SIC 1 (:2436-2439).  I021/040 (:2441-2459): ATP 3 for fields.addr bit 24, 2 for addrtype ADDR_ADSB_OTHER / _TISB_OTHER /
+ *     _ADSR_OTHER; bit 3 iff !MGPU_F_ALT_Q_BIT; one extension 0x40 iff airground == AG_GROUND.
+ *   I021/130 (:2462-2480) iff positions[i].method is MGPU_CPR_GLOBAL / _LOCAL_RECEIVER / _LOCAL_AIRCRAFT (the reference's cpr_decoded ||
+ *     sbs_pos_valid; a NULL array: no position): (int32_t)(lat / (180 / 2^23)) in double, + 2^24 if negative, three bytes each.
+ *   I021/150 (:2501-2513) iff MGPU_F_IAS_VALID or _MACH_VALID: Mach wins, (uint16_t)(mach * 1000) in double (mach is the float the
+ *     reference stored into its double), else (uint16_t)(ias / 3600.0 * 16384).  I021/151 (:2516-2520) tas.  I021/080 (:2523-2526) addr.
+ *   I021/073 (:2533-2543) iff I021/130's FSPEC bit; I021/075 (:2546-2556) and I021/160 (:2709-2718) iff MGPU_F_GS_VALID and _HEADING_VALID and
+ *     heading_type == HEADING_GROUND_TRACK: gs_v0 * 4.5511 and heading * (65536 / 360.0) in double.  I021/077 (:2721-2731) always.
+ *     The clocks: now = mstime() and time(NULL) are ONE now_ms for the whole call; midnight = now_ms / 1000 / 86400 * 86400000;
+ *     int tsm = sysTimestamp - midnight truncated to 32 bits, + 86400000 if negative, (int)(tsm * 0.128) in double; three bytes.
+ *   I021/140 (:2559-2574): geom_alt / 6.25 (UNIT_FEET) or / 20.5053 as int16_t; else iff MGPU_F_GEOM_DELTA_VALID the AIRCRAFT's
+ *     baro_alt (ac_baro_alt[i]; NULL: 0, a fresh aircraft) + fields.geom_delta (the sum wraps as a 32-bit integer), / 6.25.
+ *   I021/090 (:2576-2601) always: nac_v << 5 ADDED into an unsigned char; cpr_nucp, which nothing in the reference sets, contributes 0;
+ *     first extension nic_baro << 7 | sil << 5 (sil_type != SIL_INVALID) | nac_p << 1, second 0x20 (SIL_PER_SAMPLE) | sda << 3 | gva << 1,
+ *     each truncated to a byte.  The extensions are tested in bytes[p + 1] and only then p advances: with an empty first extension the
+ *     second's bits stand in the first's place.
+ *   I021/210 (:2604-2636) iff MGPU_OP_VALID: 2 / 1 / 0 for source SOURCE_ADSB / _ADSR / other — with MGPU_ASTERIX_REMOTE (mm->remote)
+ *     for addrtype ADDR_ADSB_ICAO, _ADSB_OTHER / ADDR_ADSR_ICAO, _ADSR_OTHER / other — | (op_version & 7) << 3 (a 3-bit field).
+ *   I021/070 (:2639-2647) squawkHex's bits as the reference shifts them.  I021/230 (:2650-2655) (int16_t)(roll * 100), a FLOAT product.
+ *   I021/145 (:2658-2665) baro_alt / 25 as integers, or (int)(baro_alt * 3.2808) iff baro_alt_unit == UNIT_METERS.
+ *   I021/152 (:2668-2674) iff MGPU_F_HEADING_VALID and heading_type == HEADING_MAGNETIC: (int)(heading * 182.0444) in double.
+ *   I021/200 (:2677-2690) iff SPI, alert, emergency or nav modes are valid.  I021/155, /157 (:2693-2706): (int16_t)(rate / 3.125) >> 1.
+ *   I021/170 (:2734-2748) callsign through char_to_ais (:212-224) over all 8 bytes (NUL and bytes outside the set: 32).
+ *   I021/020 (:2751-2819): with MGPU_F_CATEGORY_VALID and category & 7 != 0 the FSPEC bit is set and the byte written only where the
+ *     (tc, ca) pair has a case — otherwise NO byte; category & 7 == 0: a 0 byte; not valid: a 0 byte and the bit iff the AIRCRAFT's
+ *     category (ac_category[i]; NULL: 0) is 0.
+ *   I021/220 (:2822-2850) iff any of the five BDS4,4 valid flags: wind_speed, (int)wind_direction, (int16_t)(oat * 4), a FLOAT product.
+ *   I021/146 (:2853-2867) MCP wins over FMS, (int)altitude / 25.  I021/008 (:2870-2883) iff MGPU_OP_VALID and one of its bits (op_cc_tc & 3).
+ *   I021/400 (:2886-2889) the low byte of ids[i] iff ids[i] != 0 (the array mgpu_beast_encode_ex* takes; NULL: absent).
+ *   from_mlat and from_tisb are set by nothing in the reference: they suppress no record.  I021/131 and I021/295 are commented out there.
+ *   A record is at most 74 bytes (I021/152 excludes I021/075 and /160).  --net-asterix-reduce (reduce_forward is the tracker's), ASTERIX
+ *     input, CAT020 and sockets are not modelled.
+ *   Who gets a record (outputMessage calls the writer inside its first-message rule, :5846, with no aircraft and no correctedbits test,
+ *     :5882): mgpu_raw_encode_ex's rule without MGPU_RAW_NET_RULE — verdict == NULL: every message, Mode A/C included; (v & 3) ==
+ *     MGPU_GATE_FORWARD a record, MGPU_GATE_DEFER listed as {index, offset}, no record otherwise.
+ *   Domain: the reference converts doubles and floats to int, int16_t and uint16_t, undefined in C where the value does not fit.  A
+ *     message whose record is due or deferred, but one of whose scaled values to be converted (mach * 1000, roll * 100, baro_alt * 3.2808,
+ *     heading * 182.0444, gs_v0 * 4.5511, heading * (65536 / 360.0), wind_direction, oat * 4 — only those of items the record has) is
+ *     not finite or has magnitude >= 2^31, or whose position is not finite or has |lat| > 90 or |lon| > 360, gets no record, no list
+ *     entry, and adds one to *nskipped.  Inside the domain a narrowing conversion keeps the low bits of the value truncated towards
+ *     zero, which is what the reference's x86-64 build does (tests/host_stub/asterix_ref_harness.c is the judge of that).
+ *     now_ms outside [0, 253402300800000) is MGPU_E_INVAL; sysTimestamp may be any int64.
+ *   fields == NULL, host form only: the library decodes the fields itself; _device: MGPU_E_INVAL.  _device: msgs, fields, positions,
+ *     verdict, ids, ac_baro_alt, ac_category, out and deferred are device pointers; bytes, ndeferred, nskipped host pointers. */
+#define MGPU_ASTERIX_REMOTE 1u
+struct mgpu_asterix_args {
+    uint32_t size;                     /* sizeof(struct mgpu_asterix_args) */
+    uint32_t flags;                    /* MGPU_ASTERIX_REMOTE */
+    const struct mgpu_msg *msgs;
+    const struct mgpu_fields *fields;  /* [n]; NULL (host form): decoded by the library */
+    const struct mgpu_position *positions;   /* [n] or NULL */
+    const uint8_t *verdict;            /* [n] or NULL */
+    const uint64_t *ids;               /* [n] or NULL */
+    const int32_t *ac_baro_alt;        /* [n] or NULL */
+    const uint8_t *ac_category;        /* [n] or NULL */
+    uint64_t n;
+    int64_t now_ms;
+    uint8_t *out;
+    uint64_t cap;
+    uint64_t *bytes;                   /* host, out */
+    struct mgpu_deferred *deferred;    /* [deferred_cap] or NULL */
+    uint64_t deferred_cap;
+    uint64_t *ndeferred, *nskipped;    /* host, out; may be NULL (ndeferred: without verdicts) */
+};
+int mgpu_asterix_encode_ex(mgpu_ctx *ctx, const struct mgpu_asterix_args *args);
+int mgpu_asterix_encode_ex_device(mgpu_ctx *ctx, const struct mgpu_asterix_args *args);
+
 /* ---- tables, for known-answer tests against crc.c --------------------------------- */
 
 /* These run on the host (they are how the device tables are built) and need no context. */

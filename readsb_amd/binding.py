@@ -170,6 +170,17 @@ class SbsArgs(C.Structure):                                           # struct m
                 ("deferred_cap", C.c_uint64), ("ndeferred", C.POINTER(C.c_uint64)), ("nskipped", C.POINTER(C.c_uint64))]
 
 
+ASTERIX_REMOTE = 1                                                    # MGPU_ASTERIX_*
+ASTERIX_RECORD_MAX = 74                                               # bytes of a CAT021 record
+
+
+class AsterixArgs(C.Structure):                                       # struct mgpu_asterix_args
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("msgs", C.c_void_p), ("fields", C.c_void_p), ("positions", C.c_void_p),
+                ("verdict", C.c_void_p), ("ids", C.c_void_p), ("ac_baro_alt", C.c_void_p), ("ac_category", C.c_void_p), ("n", C.c_uint64),
+                ("now_ms", C.c_int64), ("out", C.c_void_p), ("cap", C.c_uint64), ("bytes", C.POINTER(C.c_uint64)), ("deferred", C.c_void_p),
+                ("deferred_cap", C.c_uint64), ("ndeferred", C.POINTER(C.c_uint64)), ("nskipped", C.POINTER(C.c_uint64))]
+
+
 class RawArgs(C.Structure):                                           # struct mgpu_raw_args
     _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("msgs", C.c_void_p), ("verdict", C.c_void_p), ("n", C.c_uint64),
                 ("out", C.c_void_p), ("cap", C.c_uint64), ("bytes", C.POINTER(C.c_uint64)), ("deferred", C.c_void_p),
@@ -351,6 +362,8 @@ def load_library():
     lib.mgpu_beast_encode_ex_device.argtypes = [vp, C.POINTER(BeastArgs)]
     lib.mgpu_sbs_encode_ex.argtypes = [vp, C.POINTER(SbsArgs)]
     lib.mgpu_sbs_encode_ex_device.argtypes = [vp, C.POINTER(SbsArgs)]
+    lib.mgpu_asterix_encode_ex.argtypes = [vp, C.POINTER(AsterixArgs)]
+    lib.mgpu_asterix_encode_ex_device.argtypes = [vp, C.POINTER(AsterixArgs)]
     lib.mgpu_raw_encode_ex.argtypes = [vp, C.POINTER(RawArgs)]
     lib.mgpu_raw_encode_ex_device.argtypes = [vp, C.POINTER(RawArgs)]
     lib.mgpu_merge_by_time.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
@@ -777,6 +790,47 @@ class Demodulator:
         a = SbsArgs(C.sizeof(SbsArgs), SBS_USE_GNSS if use_gnss else 0, d_msgs_ptr, d_fields_ptr, d_positions_ptr, d_verdict_ptr, d_geom_delta_ptr,
                     n, int(now_ms), int(override_squawk), d_out_ptr, cap, C.pointer(nb), d_deferred_ptr, deferred_cap, C.pointer(nd), C.pointer(ns))
         self._chk(self.lib.mgpu_sbs_encode_ex_device(self.ctx, C.byref(a)), "mgpu_sbs_encode_ex_device")
+        return int(nb.value), int(nd.value), int(ns.value)
+
+    def asterix_encode(self, msgs, now_ms, fields=None, positions=None, verdict=None, ids=None, ac_baro_alt=None, ac_category=None, remote=False,
+                       deferred_cap=None):
+        """mgpu_asterix_encode_ex on host arrays: the ASTERIX CAT021 target reports of a record array (include/modes_gpu.h).  fields,
+        positions, verdict as in sbs_encode (the verdict decides as for the raw lines); ids: merge_by_time's receiver ids or None;
+        ac_baro_alt (int32) / ac_category (uint8): the aircraft's state per message, None = a fresh aircraft's zeros.
+        -> (stream bytes, deferred[] records, the number of messages outside the domain)."""
+        msgs = np.ascontiguousarray(msgs)
+        assert msgs.dtype == MSG_DTYPE
+        n = len(msgs)
+
+        def arr(a, dtype):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            assert len(a) == n
+            return a
+        fields, positions, verdict = arr(fields, FIELDS_DTYPE), arr(positions, POSITION_DTYPE), arr(verdict, np.uint8)
+        ids, ac_baro_alt, ac_category = arr(ids, np.uint64), arr(ac_baro_alt, np.int32), arr(ac_category, np.uint8)
+        cap = n * ASTERIX_RECORD_MAX + 64
+        out = np.empty(cap, dtype=np.uint8)
+        dcap = int(deferred_cap if deferred_cap is not None else (n if verdict is not None else 0))
+        deferred = np.zeros(max(dcap, 1), dtype=DEFERRED_DTYPE)
+        nb, nd, ns = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        ptr = lambda a: a.ctypes.data if a is not None else None                                     # noqa: E731
+        a = AsterixArgs(C.sizeof(AsterixArgs), ASTERIX_REMOTE if remote else 0, msgs.ctypes.data, ptr(fields), ptr(positions), ptr(verdict), ptr(ids),
+                        ptr(ac_baro_alt), ptr(ac_category), n, int(now_ms), out.ctypes.data, cap, C.pointer(nb), deferred.ctypes.data, dcap,
+                        C.pointer(nd), C.pointer(ns))
+        self._chk(self.lib.mgpu_asterix_encode_ex(self.ctx, C.byref(a)), "mgpu_asterix_encode_ex")
+        return out[: nb.value].tobytes(), deferred[: nd.value].copy(), int(ns.value)
+
+    def asterix_encode_device(self, d_msgs_ptr, d_fields_ptr, n, now_ms, d_out_ptr, cap, d_positions_ptr=None, d_verdict_ptr=None, d_ids_ptr=None,
+                              d_ac_baro_alt_ptr=None, d_ac_category_ptr=None, remote=False, d_deferred_ptr=None, deferred_cap=0):
+        """mgpu_asterix_encode_ex_device: everything in HBM (pointers as ints).  -> (the stream's size in bytes, the number of deferred
+        messages, the number of skipped messages)."""
+        nb, nd, ns = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        a = AsterixArgs(C.sizeof(AsterixArgs), ASTERIX_REMOTE if remote else 0, d_msgs_ptr, d_fields_ptr, d_positions_ptr, d_verdict_ptr, d_ids_ptr,
+                        d_ac_baro_alt_ptr, d_ac_category_ptr, n, int(now_ms), d_out_ptr, cap, C.pointer(nb), d_deferred_ptr, deferred_cap,
+                        C.pointer(nd), C.pointer(ns))
+        self._chk(self.lib.mgpu_asterix_encode_ex_device(self.ctx, C.byref(a)), "mgpu_asterix_encode_ex_device")
         return int(nb.value), int(nd.value), int(ns.value)
 
     @staticmethod

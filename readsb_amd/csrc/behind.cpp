@@ -426,7 +426,7 @@ static int text_scratch(mgpu_ctx *c, uint64_t n, TextScratch *w) {
 static int text_finish(mgpu_ctx *c, const TextScratch &w, bool gated, uint64_t cap, uint64_t deferred_cap, uint64_t *bytes, uint64_t *ndeferred,
                        uint64_t *nskipped, bool skips) {
     HIPCHK(c, hipGetLastError());
-    unsigned long long total[3] = {0, 0, 0};                     // (the third is computed only for a job that can skip: SBS)
+    unsigned long long total[3] = {0, 0, 0};                     // (the third is computed only for a job that can skip: SBS, ASTERIX)
     HIPCHK(c, hipMemcpyAsync(total, w.total, (skips ? 3 : 2) * sizeof total[0], hipMemcpyDeviceToHost, c->stream_aux));
     HIPCHK(c, hipStreamSynchronize(c->stream_aux));
     *bytes = total[0];
@@ -566,6 +566,86 @@ int mgpu_raw_encode_ex(mgpu_ctx *c, const struct mgpu_raw_args *a) {
     d.deferred = b.d_deferred.as<mgpu_deferred>();
     if (int rc = raw_encode_dev(c, d)) return rc;
     return text_out_fetch(c, a->out, *a->bytes, a->deferred, gated ? a->ndeferred : nullptr);
+}
+
+// ---- ASTERIX CAT021 target reports (modesSendAsterixOutput, net_io.c:2416-2945), kernels/asterix.inc: a third job over the text outputs' scratch ----
+
+// a: every array a device pointer
+static int asterix_encode_dev(mgpu_ctx *c, const struct mgpu_asterix_args &a) {
+    TextScratch w;
+    if (int rc = text_scratch(c, a.n, &w)) return rc;
+    const TextAsterixParams p = {a.msgs, a.fields, a.positions, a.verdict, (const unsigned long long *) a.ids, a.ac_baro_alt, a.ac_category, a.now_ms, a.flags};
+    launch_asterix_encode(p, a.n, w, a.out, a.cap, a.deferred, a.verdict ? a.deferred_cap : 0, c->stream_aux);
+    return text_finish(c, w, a.verdict != nullptr, a.cap, a.deferred_cap, a.bytes, a.ndeferred, a.nskipped, true);
+}
+
+static bool asterix_args_ok(const struct mgpu_asterix_args *a, bool device) {
+    if (!a || a->size < sizeof(struct mgpu_asterix_args) || !a->bytes) return false;
+    if (a->flags & ~MGPU_ASTERIX_REMOTE) return false;
+    if (a->now_ms < 0 || a->now_ms >= 253402300800000ll) return false;       // years 1970-9999, as for the SBS lines
+    if (a->n && (!a->msgs || !a->out || (device && !a->fields))) return false;
+    if (a->verdict && (!a->ndeferred || (a->deferred_cap && !a->deferred))) return false;
+    return true;
+}
+
+// one optional host array into its staging buffer: -> the device copy through *dev (a null array stays null)
+static int asterix_stage(mgpu_ctx *c, DevBuf &buf, const void *host, uint64_t bytes, const void **dev) {
+    *dev = nullptr;
+    if (!host) return MGPU_OK;
+    if (int rc = buf.reserve(c, bytes)) return rc;
+    HIPCHK(c, hipMemcpyAsync(buf.p, host, bytes, hipMemcpyHostToDevice, c->stream_aux));
+    *dev = buf.p;
+    return MGPU_OK;
+}
+
+int mgpu_asterix_encode_ex_device(mgpu_ctx *c, const struct mgpu_asterix_args *a) {
+    if (!c || !asterix_args_ok(a, true)) return MGPU_E_INVAL;
+    *a->bytes = 0;
+    if (a->ndeferred) *a->ndeferred = 0;
+    if (a->nskipped) *a->nskipped = 0;
+    if (a->n == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return asterix_encode_dev(c, *a);
+}
+
+int mgpu_asterix_encode_ex(mgpu_ctx *c, const struct mgpu_asterix_args *a) {
+    if (!c || !asterix_args_ok(a, false)) return MGPU_E_INVAL;
+    *a->bytes = 0;
+    if (a->ndeferred) *a->ndeferred = 0;
+    if (a->nskipped) *a->nskipped = 0;
+    const uint64_t n = a->n;
+    if (n == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    Behind &b = *c->behind;
+    struct mgpu_asterix_args d = *a;
+    if (a->fields) {
+        if (int rc = stage_messages(c, a->msgs, n, a->verdict)) return rc;
+        if (int rc = b.d_fields.reserve(c, n * sizeof(mgpu_fields))) return rc;
+        HIPCHK(c, hipMemcpyAsync(b.d_fields.p, a->fields, n * sizeof(mgpu_fields), hipMemcpyHostToDevice, c->stream_aux));
+    } else {
+        if (int rc = fields_staged(c, a->msgs, n)) return rc;
+        if (a->verdict) {
+            if (int rc = b.d_beast_verdict.reserve(c, n)) return rc;
+            HIPCHK(c, hipMemcpyAsync(b.d_beast_verdict.p, a->verdict, n, hipMemcpyHostToDevice, c->stream_aux));
+        }
+    }
+    d.msgs = b.d_beast_in.as<mgpu_msg>();
+    d.fields = b.d_fields.as<mgpu_fields>();
+    if (a->verdict) d.verdict = b.d_beast_verdict.as<uint8_t>();
+    const void *d_pos, *d_ids, *d_alt, *d_cat;
+    if (int rc = asterix_stage(c, b.d_text_pos, a->positions, n * sizeof(mgpu_position), &d_pos)) return rc;
+    if (int rc = asterix_stage(c, b.d_asx_ids, a->ids, n * sizeof(uint64_t), &d_ids)) return rc;
+    if (int rc = asterix_stage(c, b.d_asx_baro_alt, a->ac_baro_alt, n * sizeof(int32_t), &d_alt)) return rc;
+    if (int rc = asterix_stage(c, b.d_asx_category, a->ac_category, n, &d_cat)) return rc;
+    d.positions = (const mgpu_position *) d_pos;
+    d.ids = (const uint64_t *) d_ids;
+    d.ac_baro_alt = (const int32_t *) d_alt;
+    d.ac_category = (const uint8_t *) d_cat;
+    if (int rc = text_out_reserve(c, a->cap, a->verdict != nullptr, a->deferred_cap)) return rc;
+    d.out = b.d_beast_out.as<uint8_t>();
+    d.deferred = b.d_deferred.as<mgpu_deferred>();
+    if (int rc = asterix_encode_dev(c, d)) return rc;
+    return text_out_fetch(c, a->out, *a->bytes, a->deferred, a->verdict ? a->ndeferred : nullptr);
 }
 
 uint32_t mgpu_crc_checksum(const uint8_t *msg, int bits) { return crc_tables().checksum(msg, bits); }

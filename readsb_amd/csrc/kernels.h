@@ -230,11 +230,25 @@ struct TextScratch {
     uint16_t *meta;                   // [n] a line's length, or the deferred mark
     uint32_t *blocks;                 // [3 * stride] per workgroup: bytes | deferred messages | skipped messages
     unsigned long long *off;          // [3 * stride] the exclusive prefix sums of the first two
-    unsigned long long *total;        // [3] the totals (skipped: SBS only)
+    unsigned long long *total;        // [3] the totals (skipped: SBS and ASTERIX only)
     size_t stride;                    // >= ceil(n / kBlock)
 };
 void launch_sbs_encode(const TextSbsParams &a, uint64_t n, const TextScratch &w, uint8_t *out, uint64_t cap, mgpu_deferred *deferred, uint64_t def_cap, hipStream_t s);
 void launch_raw_encode(const TextRawParams &a, uint64_t n, const TextScratch &w, uint8_t *out, uint64_t cap, mgpu_deferred *deferred, uint64_t def_cap, hipStream_t s);
+// ASTERIX CAT021 target reports (kernels/asterix.inc; modesSendAsterixOutput, net_io.c:2416-2945): a third job over the same passes and scratch
+struct TextAsterixParams {
+    const mgpu_msg *msgs;
+    const mgpu_fields *fields;
+    const mgpu_position *positions;
+    const uint8_t *verdict;
+    const unsigned long long *ids;    // the receiver ids of mgpu_merge_by_time
+    const int32_t *ac_baro_alt;       // the aircraft's state: a->baro_alt, a->category
+    const uint8_t *ac_category;
+    int64_t now_ms;
+    uint32_t flags;                   // MGPU_ASTERIX_*
+};
+void launch_asterix_encode(const TextAsterixParams &a, uint64_t n, const TextScratch &w, uint8_t *out, uint64_t cap, mgpu_deferred *deferred, uint64_t def_cap,
+                           hipStream_t s);
 // stable merge of message lists by timestamp (kernels/merge.inc): segs [nseg] in device memory, scratch = merge_scratch_bytes(n, nseg)
 struct MergeSeg {
     const mgpu_msg *msgs;

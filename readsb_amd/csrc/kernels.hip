@@ -11,7 +11,8 @@
 //   k_window_stats   what the skip-ahead hid from the counters (demod_2400.c:468)
 //   k_modeac*, k_beast_*, k_decode_fields: Mode A/C demodulator, beast wire encoder, per-message field decode
 //   k_gate_*, k_cpr_*  first stage of the tracker, CPR pairing and position decode over the message list (track.c, cpr.c)
-//   k_text_*         SBS and AVR raw text lines of the message list (net_io.c:3184-3404, 1837-1863)
+//   k_text_*         SBS and AVR raw text lines of the message list (net_io.c:3184-3404, 1837-1863), and its ASTERIX CAT021
+//                    target reports (net_io.c:2416-2945) as a third job of the same passes
 //
 // No MFMA anywhere: this is HBM-bound integer/byte streaming work.  All arithmetic on the
 // message path is integer and bit-exact with the reference; the SC16 converters use IEEE float
@@ -123,6 +124,7 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 #endif
 #include "kernels/beast.inc"
 #include "kernels/text.inc"
+#include "kernels/asterix.inc"
 #include "kernels/fields.inc"
 #include "kernels/gate.inc"
 #include "kernels/merge.inc"

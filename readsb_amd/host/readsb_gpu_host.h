@@ -83,8 +83,9 @@ int gpu_ifile_run_until(struct gpu_demod *g, int fd, input_format_t format, unsi
 
 /* readsb_gpu_ifile --sbs-out (sbs_gpu.c): every chunk of the file a deferred feed whose records stay in HBM, then field decode, tracking
  * gate, position decode and mgpu_sbs_encode_ex_device on them; only the lines come back and go to `path`.  Messages the gate defers
- * to a position tracker are dropped.  now_ms: fields 9 and 10.  counters: the demodulator's, at the end. */
-struct gpu_sbs_opts { const char *path; int64_t now_ms; int have_ref, gnss; double lat, lon; };
+ * to a position tracker are dropped.  now_ms: fields 9 and 10.  counters: the demodulator's, at the end.
+ * asterix (--asterix-out): the chain ends in mgpu_asterix_encode_ex_device instead, `path` receives the ASTERIX CAT021 stream. */
+struct gpu_sbs_opts { const char *path; int64_t now_ms; int have_ref, gnss; double lat, lon; int asterix; };
 int gpu_sbs_run(mgpu_ctx *ctx, int fd, input_format_t format, unsigned chunk_buffers, const struct gpu_sbs_opts *o, struct mgpu_counters *counters);
 
 /* ---- fan-in: many sample streams, one demodulator context each -------------------------------

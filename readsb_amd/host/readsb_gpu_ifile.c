@@ -4,6 +4,7 @@
  * and with --stats the demodulator counters of display_stats (stats.c:65-125).
  * --sbs-out PATH: instead of the raw lines, the BaseStation feed of the capture (modesSendSBSOutput, net_io.c:3184-3404) into PATH,
  * with nothing but the text leaving the GPU: feed -> field decode -> tracking gate -> position decode -> SBS encoder (sbs_gpu.c).
+ * --asterix-out PATH: the same chain ending in the ASTERIX CAT021 encoder (modesSendAsterixOutput, net_io.c:2416-2945).
  */
 #include <fcntl.h>
 #include <inttypes.h>
@@ -33,12 +34,16 @@ static const char usage[] =
     "readsb_gpu_ifile --ifile PATH|- [--iformat UC8|SC16|SC16Q11] [--fix|--no-fix|--aggressive] [--no-fix-df] [--modeac]\n"
     "                 [--preamble-threshold N] [--gpu-device N] [--gpu-chunk-buffers N] [--startup-time-ms MS] [--stats] [--raw --mlat]\n"
     "                 [--sbs-out PATH [--sbs-now-ms MS] [--lat DEG --lon DEG] [--gnss]]\n"
+    "                 [--asterix-out PATH [--asterix-now-ms MS] [--lat DEG --lon DEG]]\n"
     "  default: one `@<timestamp><frame>;` line per accepted message on stdout (readsb --raw --mlat)\n"
     "  --sbs-out PATH   write the BaseStation (port 30003) lines of the capture to PATH instead; the messages, their field records,\n"
     "                   the tracking gate's verdicts and the decoded positions stay on the GPU, only the text comes back.\n"
     "                   Messages whose forwarding is the position tracker's decision (deferred by the gate) are DROPPED, as\n"
     "                   readsb_gpu_gather --forward-only drops them; their number is reported on stderr.  Not with --modeac.\n"
     "  --sbs-now-ms MS  the time printed in fields 9 and 10 (ms since 1970; default: the clock when the program starts)\n"
+    "  --asterix-out PATH  write the ASTERIX CAT021 target reports of the capture (the asterix_out connector's stream) to PATH instead,\n"
+    "                   by the same resident chain; deferred messages are DROPPED likewise.  No receiver ids, fresh aircraft state.\n"
+    "  --asterix-now-ms MS  the clock of I021/077 and of the day's midnight (ms since 1970; default: the clock when the program starts)\n"
     "  --lat, --lon     the receiver's location (enables positions relative to the receiver and surface positions)\n"
     "  --gnss           Modes.use_gnss: geometric altitudes and rates with the H suffix where available\n";
 
@@ -52,7 +57,7 @@ int main(int argc, char **argv) {
     input_format_t fmt = INPUT_UC8;
     int stats = 0;
     unsigned chunk = 256;
-    struct gpu_sbs_opts sbs = {NULL, -1, 0, 0, 0.0, 0.0};
+    struct gpu_sbs_opts sbs = {NULL, -1, 0, 0, 0.0, 0.0, 0};
     int have_lat = 0, have_lon = 0;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--ifile") && i + 1 < argc) ifile = argv[++i];
@@ -69,8 +74,9 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--gpu-chunk-buffers") && i + 1 < argc) chunk = (unsigned) atoi(argv[++i]);
         else if (!strcmp(argv[i], "--startup-time-ms") && i + 1 < argc) cfg.startup_time_ms = atoll(argv[++i]);
         else if (!strcmp(argv[i], "--stats")) stats = 1;
-        else if (!strcmp(argv[i], "--sbs-out") && i + 1 < argc) sbs.path = argv[++i];
-        else if (!strcmp(argv[i], "--sbs-now-ms") && i + 1 < argc) sbs.now_ms = atoll(argv[++i]);
+        else if (!strcmp(argv[i], "--sbs-out") && i + 1 < argc) { sbs.path = argv[++i]; sbs.asterix = 0; }
+        else if (!strcmp(argv[i], "--asterix-out") && i + 1 < argc) { sbs.path = argv[++i]; sbs.asterix = 1; }
+        else if ((!strcmp(argv[i], "--sbs-now-ms") || !strcmp(argv[i], "--asterix-now-ms")) && i + 1 < argc) sbs.now_ms = atoll(argv[++i]);
         else if (!strcmp(argv[i], "--lat") && i + 1 < argc) { sbs.lat = atof(argv[++i]); have_lat = 1; }
         else if (!strcmp(argv[i], "--lon") && i + 1 < argc) { sbs.lon = atof(argv[++i]); have_lon = 1; }
         else if (!strcmp(argv[i], "--gnss")) sbs.gnss = 1;
@@ -80,8 +86,8 @@ int main(int argc, char **argv) {
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     sbs.have_ref = have_lat && have_lon;
-    if (sbs.path && !gpu_sbs_run) { fprintf(stderr, "--sbs-out: this build has no GPU chain\n"); return 2; }
-    if (sbs.path && cfg.mode_ac) { fprintf(stderr, "--sbs-out: not with --modeac (its replies are merged on the host)\n"); return 2; }
+    if (sbs.path && !gpu_sbs_run) { fprintf(stderr, "--sbs-out / --asterix-out: this build has no GPU chain\n"); return 2; }
+    if (sbs.path && cfg.mode_ac) { fprintf(stderr, "--sbs-out / --asterix-out: not with --modeac (its replies are merged on the host)\n"); return 2; }
     if (sbs.path && sbs.now_ms < 0) {
         struct timespec ts;
         clock_gettime(CLOCK_REALTIME, &ts);

@@ -1,5 +1,7 @@
 /* sbs_gpu.c — the BaseStation feed of a sample file with everything resident (readsb_gpu_ifile --sbs-out): what outputMessage's
- * SBS branch (net_io.c:5846-5857, modesSendSBSOutput :3184-3404) writes for the capture, with deferred messages dropped. */
+ * SBS branch (net_io.c:5846-5857, modesSendSBSOutput :3184-3404) writes for the capture, with deferred messages dropped.
+ * With opts.asterix (--asterix-out) the same chain ends in mgpu_asterix_encode_ex_device: the ASTERIX CAT021 stream of the capture
+ * (:5882, modesSendAsterixOutput :2416-2945), no receiver ids and fresh aircraft state. */
 #define __HIP_PLATFORM_AMD__ 1
 #include <inttypes.h>
 #include <stdio.h>
@@ -57,14 +59,25 @@ int gpu_sbs_run(mgpu_ctx *ctx, int fd, input_format_t fmt, unsigned chunk_buffer
         SBS_MGPU(mgpu_track_gate_device(ctx, d_msgs, d_fields, n, d_verdict));
         SBS_MGPU(mgpu_cpr_track_device(ctx, &cpr, d_msgs, d_fields, n, d_pos));
         uint64_t bytes = 0, nd = 0, ns = 0;
-        struct mgpu_sbs_args a;
-        memset(&a, 0, sizeof a);
-        a.size = sizeof a; a.flags = o->gnss ? MGPU_SBS_USE_GNSS : 0;
-        a.msgs = d_msgs; a.fields = d_fields; a.positions = d_pos; a.verdict = d_verdict; a.n = n;
-        a.now_ms = o->now_ms; a.override_squawk = -1;
-        a.out = d_text; a.cap = cap * 176; a.bytes = &bytes;
-        a.deferred = d_def; a.deferred_cap = cap; a.ndeferred = &nd; a.nskipped = &ns;      /* listed, then dropped */
-        SBS_MGPU(mgpu_sbs_encode_ex_device(ctx, &a));
+        if (o->asterix) {
+            struct mgpu_asterix_args a;
+            memset(&a, 0, sizeof a);
+            a.size = sizeof a;
+            a.msgs = d_msgs; a.fields = d_fields; a.positions = d_pos; a.verdict = d_verdict; a.n = n;
+            a.now_ms = o->now_ms;
+            a.out = d_text; a.cap = cap * 176; a.bytes = &bytes;                               /* (a record is at most 74 bytes) */
+            a.deferred = d_def; a.deferred_cap = cap; a.ndeferred = &nd; a.nskipped = &ns;
+            SBS_MGPU(mgpu_asterix_encode_ex_device(ctx, &a));
+        } else {
+            struct mgpu_sbs_args a;
+            memset(&a, 0, sizeof a);
+            a.size = sizeof a; a.flags = o->gnss ? MGPU_SBS_USE_GNSS : 0;
+            a.msgs = d_msgs; a.fields = d_fields; a.positions = d_pos; a.verdict = d_verdict; a.n = n;
+            a.now_ms = o->now_ms; a.override_squawk = -1;
+            a.out = d_text; a.cap = cap * 176; a.bytes = &bytes;
+            a.deferred = d_def; a.deferred_cap = cap; a.ndeferred = &nd; a.nskipped = &ns;      /* listed, then dropped */
+            SBS_MGPU(mgpu_sbs_encode_ex_device(ctx, &a));
+        }
         if (bytes > text_cap) {
             free(text);
             text_cap = bytes + bytes / 4;
@@ -84,8 +97,12 @@ int gpu_sbs_run(mgpu_ctx *ctx, int fd, input_format_t fmt, unsigned chunk_buffer
     }
     (void) hipFree(d_fields); (void) hipFree(d_pos); (void) hipFree(d_def); (void) hipFree(d_verdict); (void) hipFree(d_text);
     free(text); free(buf);
-    fprintf(stderr, "sbs: %" PRIu64 " messages, %" PRIu64 " bytes of lines, %" PRIu64 " message(s) left to a position tracker dropped, %" PRIu64
-            " outside the printable domain\n", nmsg, lines_bytes, dropped, skipped);
+    if (o->asterix)
+        fprintf(stderr, "asterix: %" PRIu64 " messages, %" PRIu64 " bytes of records, %" PRIu64 " message(s) left to a position tracker dropped, %" PRIu64
+                " outside the domain\n", nmsg, lines_bytes, dropped, skipped);
+    else
+        fprintf(stderr, "sbs: %" PRIu64 " messages, %" PRIu64 " bytes of lines, %" PRIu64 " message(s) left to a position tracker dropped, %" PRIu64
+                " outside the printable domain\n", nmsg, lines_bytes, dropped, skipped);
     return fclose(out) ? MGPU_E_INVAL : MGPU_OK;
 }
 

@@ -1,7 +1,8 @@
-"""Throughput of the two text outputs — mgpu_sbs_encode_ex_device and mgpu_raw_encode_ex_device (kernels/text.inc) — on records
+"""Throughput of the outputs behind the list — mgpu_sbs_encode_ex_device and mgpu_raw_encode_ex_device (kernels/text.inc) and
+mgpu_asterix_encode_ex_device (kernels/asterix.inc, the ASTERIX CAT021 target reports: same inputs, same run) — on records
 resident in HBM, the record set of tools/bench_behind.py run through the field decode, the gate and the position decode first, with
 the beast encoder (k_beast_size + k_beast_write) on the same records in the same process for scale
-(python tools/bench_text.py [--messages N] [--harness PATH] | --build-harness DIR).  Prints one JSON line per output: microseconds per call, lines and
+(python tools/bench_text.py [--messages N] [--harness PATH] | --build-harness DIR).  Prints one JSON line per output: microseconds per call, milliseconds per 1 M messages, lines and
 bytes written per second, nanoseconds per output byte.  Wall clock around the C-ABI `_device` calls (launch + stream sync + the read-back
 of the totals included); run it under `rocprofv3 --kernel-trace --stats` for the kernels' own durations.
 --build-harness DIR builds the reference's own writers (tests/sbs_util.py: build_ref_harness; needs the full reference build of
@@ -69,6 +70,8 @@ def main():
     d = readsb_amd.Demodulator(max_samples=1 << 20)
     d_in, d_f, d_v, d_p = malloc(n * 64), malloc(n * fb), malloc(n), malloc(n * pb)
     d_sbs, d_raw, d_beast = malloc(n * su.SBS_LINE_MAX), malloc(n * su.RAW_LINE_MAX), malloc(n * 44)
+    asx_max = readsb_amd.binding.ASTERIX_RECORD_MAX
+    d_asx = malloc(n * asx_max)
     d_def = malloc(n * 16)
     for k in range(reps_in):
         assert hip.hipMemcpy(d_in + k * m.nbytes, m.ctypes.data, m.nbytes, 1) == 0
@@ -82,6 +85,11 @@ def main():
                                      deferred_cap=n)),
         ("mgpu_sbs_encode_ex_device (every message, positions)",
          lambda: d.sbs_encode_device(d_in, d_f, n, su.NOW_MS, d_sbs, n * su.SBS_LINE_MAX, d_positions_ptr=d_p)),
+        ("mgpu_asterix_encode_ex_device (gate verdicts, positions)",
+         lambda: d.asterix_encode_device(d_in, d_f, n, su.NOW_MS, d_asx, n * asx_max, d_positions_ptr=d_p, d_verdict_ptr=d_v, d_deferred_ptr=d_def,
+                                         deferred_cap=n)),
+        ("mgpu_asterix_encode_ex_device (every message, positions)",
+         lambda: d.asterix_encode_device(d_in, d_f, n, su.NOW_MS, d_asx, n * asx_max, d_positions_ptr=d_p)),
         ("mgpu_raw_encode_ex_device (mlat, every message)", lambda: d.raw_encode_device(d_in, n, d_raw, n * su.RAW_LINE_MAX, mlat=True)),
         ("mgpu_beast_encode_device (k_beast_size + k_beast_write)", lambda: (d.beast_encode_device(d_in, n, d_beast, n * 44),)),
     )
@@ -90,6 +98,7 @@ def main():
         nbytes = int(out[0])
         print(json.dumps({"output": name, "messages": n, "bytes": nbytes, "deferred": int(out[1]) if len(out) > 1 else 0,
                           "skipped": int(out[2]) if len(out) > 2 else 0, "us_per_call": round(med * 1e6, 1), "us_per_call_best": round(best * 1e6, 1),
+                          "ms_per_1M_messages": round(med * 1e3 * 1e6 / n, 4),
                           "messages_per_s": round(n / med), "bytes_per_s": round(nbytes / med), "ns_per_output_byte": round(med * 1e9 / max(nbytes, 1), 4),
                           "reps": a.reps, "timing": "median wall clock around the C-ABI call, launch + sync included"}), flush=True)
     if a.harness:
