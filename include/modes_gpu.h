@@ -939,6 +939,37 @@ struct mgpu_asterix_args {
 int mgpu_asterix_encode_ex(mgpu_ctx *ctx, const struct mgpu_asterix_args *args);
 int mgpu_asterix_encode_ex_device(mgpu_ctx *ctx, const struct mgpu_asterix_args *args);
 
+/* ---- snip: strip quiet stretches from a UC8 capture (snipMode, readsb.c:1187-1206; `readsb --snip <level>`, :1581-1583) ----------
+ *
+ * A sample is two bytes (i, q); it is quiet iff abs(i - 127) < level && abs(q - 127) < level in int arithmetic (:1197) — level <= 0:
+ * nothing is quiet, level >= 129: everything is.  A counter c (uint64_t, 0 at the start of a stream, :1194) counts the quiet samples
+ * since the last one that was not; a quiet sample is dropped iff c > 32 (MODES_PREAMBLE_SIZE) after counting it (:1198-1199), every
+ * other sample is kept, in order, with its bytes (:1203-1204).  A trailing odd byte is the caller's to drop (:1196 reads pairs).
+ *   *quiet_run is that c: read before the call, written after it, so that a stream cut into any calls gives the bytes and the final c
+ *     of one call.  NULL: a fresh stream (c = 0) whose state is dropped.
+ *   The context's format is irrelevant: snip is defined on bytes.  The calls run on the stream of the other synchronous entries and
+ *     do not wait for queued feeds.
+ *   args->size smaller than sizeof(struct mgpu_snip_args), NULL ctx, args or nout, out overlapping iq: MGPU_E_INVAL.  nsamples == 0:
+ *     MGPU_OK, *nout = 0, *quiet_run unchanged.  More kept than cap_samples: MGPU_E_OVERFLOW with *nout = what is needed, nothing
+ *     stored at or beyond out + 2 * cap_samples, *quiet_run unchanged.
+ *   mgpu_snip: iq and out in host memory; the input goes through the library's device scratch in passes of pass_samples samples
+ *     (0: the library's default), so it may be larger than the device's memory.
+ *   mgpu_snip_device: iq and out device pointers, iq 16-byte aligned (MGPU_E_INVAL otherwise), out 2-byte aligned — successive calls
+ *     can append into one buffer; pass_samples is ignored.  nout and quiet_run are host pointers in both. */
+struct mgpu_snip_args {
+    uint32_t size;                     /* sizeof(struct mgpu_snip_args) */
+    int32_t level;
+    const uint8_t *iq;                 /* nsamples x 2 bytes */
+    uint64_t nsamples;
+    uint8_t *out;                      /* cap_samples x 2 bytes; must not overlap iq */
+    uint64_t cap_samples;
+    uint64_t *nout;                    /* host, out: samples kept */
+    uint64_t *quiet_run;               /* host, in/out: the reference's c; NULL = a fresh stream whose state is dropped */
+    uint64_t pass_samples;             /* host form: samples staged per pass; 0 = the library's default */
+};
+int mgpu_snip(mgpu_ctx *ctx, const struct mgpu_snip_args *args);
+int mgpu_snip_device(mgpu_ctx *ctx, const struct mgpu_snip_args *args);
+
 /* ---- tables, for known-answer tests against crc.c --------------------------------- */
 
 /* These run on the host (they are how the device tables are built) and need no context. */

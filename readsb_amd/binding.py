@@ -187,6 +187,11 @@ class RawArgs(C.Structure):                                           # struct m
                 ("deferred_cap", C.c_uint64), ("ndeferred", C.POINTER(C.c_uint64))]
 
 
+class SnipArgs(C.Structure):                                          # struct mgpu_snip_args
+    _fields_ = [("size", C.c_uint32), ("level", C.c_int32), ("iq", C.c_void_p), ("nsamples", C.c_uint64), ("out", C.c_void_p),
+                ("cap_samples", C.c_uint64), ("nout", C.POINTER(C.c_uint64)), ("quiet_run", C.POINTER(C.c_uint64)), ("pass_samples", C.c_uint64)]
+
+
 ABI_VERSION = 6                             # MGPU_ABI_VERSION of the include/modes_gpu.h these ctypes mirrors were written against
 
 
@@ -366,6 +371,8 @@ def load_library():
     lib.mgpu_asterix_encode_ex_device.argtypes = [vp, C.POINTER(AsterixArgs)]
     lib.mgpu_raw_encode_ex.argtypes = [vp, C.POINTER(RawArgs)]
     lib.mgpu_raw_encode_ex_device.argtypes = [vp, C.POINTER(RawArgs)]
+    lib.mgpu_snip.argtypes = [vp, C.POINTER(SnipArgs)]
+    lib.mgpu_snip_device.argtypes = [vp, C.POINTER(SnipArgs)]
     lib.mgpu_merge_by_time.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
     lib.mgpu_merge_by_time_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
     lib.mgpu_merge_last_passes.argtypes = [vp]
@@ -864,6 +871,26 @@ class Demodulator:
                     d_deferred_ptr, deferred_cap, C.pointer(nd))
         self._chk(self.lib.mgpu_raw_encode_ex_device(self.ctx, C.byref(a)), "mgpu_raw_encode_ex_device")
         return int(nb.value), int(nd.value)
+
+    def snip(self, iq, level, quiet_run=0, pass_samples=0):
+        """mgpu_snip on a host array of UC8 bytes (`readsb --snip level`): every stretch of quiet samples cut down to its first 32.  A
+        trailing odd byte is dropped.  quiet_run: the counter a stream's earlier calls left (0: a fresh stream); pass_samples: samples
+        staged per pass (0: the library's default).  -> (the kept bytes as a uint8 array, the counter for the stream's next call)."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8).reshape(-1)
+        n = iq.size // 2
+        out = np.empty(2 * n, dtype=np.uint8)
+        nout, run = C.c_uint64(0), C.c_uint64(int(quiet_run))
+        a = SnipArgs(C.sizeof(SnipArgs), int(level), iq.ctypes.data, n, out.ctypes.data, n, C.pointer(nout), C.pointer(run), int(pass_samples))
+        self._chk(self.lib.mgpu_snip(self.ctx, C.byref(a)), "mgpu_snip")
+        return out[: 2 * nout.value].copy(), int(run.value)
+
+    def snip_device(self, d_iq_ptr, nsamples, level, d_out_ptr, cap_samples, quiet_run=0):
+        """mgpu_snip_device: samples and output in HBM (pointers as ints; the samples 16-byte aligned, the output 2-byte aligned).
+        -> (samples kept, the counter for the stream's next call)."""
+        nout, run = C.c_uint64(0), C.c_uint64(int(quiet_run))
+        a = SnipArgs(C.sizeof(SnipArgs), int(level), d_iq_ptr, int(nsamples), d_out_ptr, int(cap_samples), C.pointer(nout), C.pointer(run), 0)
+        self._chk(self.lib.mgpu_snip_device(self.ctx, C.byref(a)), "mgpu_snip_device")
+        return int(nout.value), int(run.value)
 
     def merge_by_time(self, lists, ids=None, verdicts=None):
         """mgpu_merge_by_time on host arrays: the receivers' lists merged by timestamp on the GPU, equal stamps in input order —

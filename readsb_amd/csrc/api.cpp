@@ -5,6 +5,7 @@
 // The product has no CPU compute path: without a usable HIP device mgpu_create() fails with
 // MGPU_E_NODEVICE.
 #include "behind.h"
+#include "snip.h"
 
 // Wait for `pred` (evaluated under c->mu).  During a feed: poll with the lock released and the core offered to others;
 // otherwise block on the condition variable.
@@ -346,7 +347,8 @@ int mgpu_create(const struct mgpu_config *cfg, mgpu_ctx **out) {
     mgpu_ctx *c = new (std::nothrow) mgpu_ctx();
     if (!c) return MGPU_E_NOMEM;
     c->behind.reset(new (std::nothrow) Behind());
-    if (!c->behind) { delete c; return MGPU_E_NOMEM; }
+    c->snip.reset(new (std::nothrow) Snip());
+    if (!c->behind || !c->snip) { delete c; return MGPU_E_NOMEM; }
     c->cfg = *cfg;
     if (hipSetDevice(cfg->device) != hipSuccess) { delete c; return MGPU_E_NODEVICE; }
     // the second stream (what follows a chunk's walk; the SC16 formats' float sums) at the lowest priority the device offers: its
@@ -508,6 +510,7 @@ void mgpu_destroy(mgpu_ctx *c) {
     for (void *p : dev)
         if (p) (void) hipFree(p);
     c->behind.reset();                                        // everything behind the message list (behind.h), before its stream goes
+    c->snip.reset();
     if (c->stream) (void) hipStreamDestroy(c->stream);
     if (c->stream2) (void) hipStreamDestroy(c->stream2);
     if (c->stream_w) (void) hipStreamDestroy(c->stream_w);

@@ -33,6 +33,7 @@
 using namespace mgpu;
 
 struct Behind;                                                // behind.h
+struct Snip;                                                  // snip.h
 
 constexpr int kPacketWords = 12;                              // header of a shard packet, 64-bit words: stream position, samples, live records,
 constexpr uint64_t kPacketMagic = 0x3354454b4341504dull;      // magic, candidates, phases 4/5, 6/7, 8 tried, conditional-only / unconditional candidates, buffers, 0
@@ -415,6 +416,7 @@ struct mgpu_ctx {
     uint64_t wk_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};          // chunks, taken from the device, not converged, premises failed (host walk), refused, walks, mismatches, -
     hipStream_t stream_aux = nullptr;                         // field decode / beast encoder / tracking gate: synchronous calls, not behind the pipeline's queued chunks
     std::unique_ptr<Behind> behind;                           // ... and their device state (behind.h)
+    std::unique_ptr<Snip> snip;                               // mgpu_snip's (snip.h)
     uint16_t *d_hist = nullptr;                               // magnitudes of the 326 samples before the shard
     uint8_t *d_hist_iq = nullptr;
     unsigned long long *d_hist_sums = nullptr;

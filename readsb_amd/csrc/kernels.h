@@ -249,6 +249,18 @@ struct TextAsterixParams {
 };
 void launch_asterix_encode(const TextAsterixParams &a, uint64_t n, const TextScratch &w, uint8_t *out, uint64_t cap, mgpu_deferred *deferred, uint64_t def_cap,
                            hipStream_t s);
+// `readsb --snip` over UC8 samples (kernels/snip.inc; snipMode, readsb.c:1187-1206)
+constexpr uint64_t kSnipTileSamples = 8192;   // samples per tile of its passes, and per workgroup: consecutive tiles
+constexpr uint64_t kSnipGroupSamples = 4 * kSnipTileSamples;
+struct SnipScratch {
+    unsigned long long *masks;        // [stride * kSnipGroupSamples / 64] the keep masks, a bit per sample
+    uint32_t *blocks;                 // [2 * stride] per workgroup: samples kept | 1 + the tile's last loud sample (0: none)
+    unsigned long long *off;          // [stride] the exclusive prefix sums of the first
+    unsigned long long *total;        // [2] samples kept; 1 + the call's last loud sample (0: none)
+    size_t stride;                    // >= ceil(n / kSnipGroupSamples)
+};
+// iq 16-byte aligned, out 2-byte aligned; quiet_run: the reference's counter before the call; write == false: the counts only
+void launch_snip(const uint8_t *iq, uint64_t n, int32_t level, uint64_t quiet_run, const SnipScratch &w, uint8_t *out, uint64_t cap, bool write, hipStream_t s);
 // stable merge of message lists by timestamp (kernels/merge.inc): segs [nseg] in device memory, scratch = merge_scratch_bytes(n, nseg)
 struct MergeSeg {
     const mgpu_msg *msgs;

@@ -13,6 +13,7 @@
 //   k_gate_*, k_cpr_*  first stage of the tracker, CPR pairing and position decode over the message list (track.c, cpr.c)
 //   k_text_*         SBS and AVR raw text lines of the message list (net_io.c:3184-3404, 1837-1863), and its ASTERIX CAT021
 //                    target reports (net_io.c:2416-2945) as a third job of the same passes
+//   k_snip_*         `--snip`: quiet stretches of a UC8 capture cut down to their first 32 samples (readsb.c:1187-1206)
 //
 // No MFMA anywhere: this is HBM-bound integer/byte streaming work.  All arithmetic on the
 // message path is integer and bit-exact with the reference; the SC16 converters use IEEE float
@@ -21,6 +22,7 @@
 // libmodes_gpu_exp.so) adds the ordered walk on the device and the A/B switches of DESIGN.md §7.
 #include "kernels.h"
 #include "tables.h"
+#include "snip_mask.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -125,6 +127,7 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 #include "kernels/beast.inc"
 #include "kernels/text.inc"
 #include "kernels/asterix.inc"
+#include "kernels/snip.inc"
 #include "kernels/fields.inc"
 #include "kernels/gate.inc"
 #include "kernels/merge.inc"

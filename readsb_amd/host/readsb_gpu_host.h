@@ -88,6 +88,10 @@ int gpu_ifile_run_until(struct gpu_demod *g, int fd, input_format_t format, unsi
 struct gpu_sbs_opts { const char *path; int64_t now_ms; int have_ref, gnss; double lat, lon; int asterix; };
 int gpu_sbs_run(mgpu_ctx *ctx, int fd, input_format_t format, unsigned chunk_buffers, const struct gpu_sbs_opts *o, struct mgpu_counters *counters);
 
+/* readsb_gpu_ifile --snip LEVEL (snip_gpu.c): `readsb --snip <level>` (snipMode, readsb.c:1187-1206) through mgpu_snip — the UC8 bytes
+ * of `fd` with every quiet stretch cut down to its first 32 samples, to stdout.  cfg: the device to use.  0 or a negative MGPU_E_* code. */
+int gpu_snip_run(const struct mgpu_config *cfg, int fd, int level);
+
 /* ---- fan-in: many sample streams, one demodulator context each -------------------------------
  * The aggregator's input side (README.md:40-51: several receivers feeding one readsb): an sdr_handler-shaped row
  * (sdr.c:94-122: initConfig / handleOption / open / run / cancel / close) that takes any number of `--ifile`s.  Every

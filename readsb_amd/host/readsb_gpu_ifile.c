@@ -5,6 +5,7 @@
  * --sbs-out PATH: instead of the raw lines, the BaseStation feed of the capture (modesSendSBSOutput, net_io.c:3184-3404) into PATH,
  * with nothing but the text leaving the GPU: feed -> field decode -> tracking gate -> position decode -> SBS encoder (sbs_gpu.c).
  * --asterix-out PATH: the same chain ending in the ASTERIX CAT021 encoder (modesSendAsterixOutput, net_io.c:2416-2945).
+ * --snip LEVEL: `readsb --snip <level>` (snipMode, readsb.c:1187-1206) instead of demodulating: stdin (or --ifile) to stdout (snip_gpu.c).
  */
 #include <fcntl.h>
 #include <inttypes.h>
@@ -35,6 +36,7 @@ static const char usage[] =
     "                 [--preamble-threshold N] [--gpu-device N] [--gpu-chunk-buffers N] [--startup-time-ms MS] [--stats] [--raw --mlat]\n"
     "                 [--sbs-out PATH [--sbs-now-ms MS] [--lat DEG --lon DEG] [--gnss]]\n"
     "                 [--asterix-out PATH [--asterix-now-ms MS] [--lat DEG --lon DEG]]\n"
+    "readsb_gpu_ifile --snip LEVEL [--ifile PATH|-] [--gpu-device N]\n"
     "  default: one `@<timestamp><frame>;` line per accepted message on stdout (readsb --raw --mlat)\n"
     "  --sbs-out PATH   write the BaseStation (port 30003) lines of the capture to PATH instead; the messages, their field records,\n"
     "                   the tracking gate's verdicts and the decoded positions stay on the GPU, only the text comes back.\n"
@@ -45,10 +47,14 @@ static const char usage[] =
     "                   by the same resident chain; deferred messages are DROPPED likewise.  No receiver ids, fresh aircraft state.\n"
     "  --asterix-now-ms MS  the clock of I021/077 and of the day's midnight (ms since 1970; default: the clock when the program starts)\n"
     "  --lat, --lon     the receiver's location (enables positions relative to the receiver and surface positions)\n"
-    "  --gnss           Modes.use_gnss: geometric altitudes and rates with the H suffix where available\n";
+    "  --gnss           Modes.use_gnss: geometric altitudes and rates with the H suffix where available\n"
+    "  --snip LEVEL     readsb --snip: copy UC8 samples from stdin (or --ifile PATH) to stdout, every stretch of samples with\n"
+    "                   |I - 127| < LEVEL and |Q - 127| < LEVEL cut down to its first 32; nothing is demodulated\n";
 
 /* readsb_amd/host/sbs_gpu.c; absent from builds against a stand-in library, which have no device to keep anything on */
 #pragma weak gpu_sbs_run
+/* readsb_amd/host/snip_gpu.c; absent likewise (a stand-in library has no mgpu_snip) */
+#pragma weak gpu_snip_run
 
 int main(int argc, char **argv) {
     struct mgpu_config cfg;
@@ -58,7 +64,7 @@ int main(int argc, char **argv) {
     int stats = 0;
     unsigned chunk = 256;
     struct gpu_sbs_opts sbs = {NULL, -1, 0, 0, 0.0, 0.0, 0};
-    int have_lat = 0, have_lon = 0;
+    int have_lat = 0, have_lon = 0, snip = 0, snip_level = 0;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--ifile") && i + 1 < argc) ifile = argv[++i];
         else if (!strcmp(argv[i], "--iformat") && i + 1 < argc) {
@@ -80,10 +86,19 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--lat") && i + 1 < argc) { sbs.lat = atof(argv[++i]); have_lat = 1; }
         else if (!strcmp(argv[i], "--lon") && i + 1 < argc) { sbs.lon = atof(argv[++i]); have_lon = 1; }
         else if (!strcmp(argv[i], "--gnss")) sbs.gnss = 1;
+        else if (!strcmp(argv[i], "--snip") && i + 1 < argc) { snip = 1; snip_level = atoi(argv[++i]); }     /* readsb.c:1581-1583 */
         else if (!strcmp(argv[i], "--help")) { fputs(usage, stdout); return 0; }
         else if (!strcmp(argv[i], "--raw") || !strcmp(argv[i], "--mlat") || !strcmp(argv[i], "--quiet")) { }
         else if (!strcmp(argv[i], "--device-type") && i + 1 < argc) ++i;
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
+    }
+    if (snip) {
+        if (!gpu_snip_run) { fprintf(stderr, "--snip: this build has no GPU chain\n"); return 2; }
+        int sfd = !ifile || !strcmp(ifile, "-") ? STDIN_FILENO : open(ifile, O_RDONLY);
+        if (sfd < 0) { perror(ifile); return 1; }
+        int src = gpu_snip_run(&cfg, sfd, snip_level);
+        if (sfd != STDIN_FILENO) close(sfd);
+        return src == MGPU_OK ? 0 : 1;
     }
     sbs.have_ref = have_lat && have_lon;
     if (sbs.path && !gpu_sbs_run) { fprintf(stderr, "--sbs-out / --asterix-out: this build has no GPU chain\n"); return 2; }
