@@ -939,6 +939,70 @@ struct mgpu_asterix_args {
 int mgpu_asterix_encode_ex(mgpu_ctx *ctx, const struct mgpu_asterix_args *args);
 int mgpu_asterix_encode_ex_device(mgpu_ctx *ctx, const struct mgpu_asterix_args *args);
 
+/* ---- the decoded-message dump (kernels/dump.inc, csrc/dump_format.h) ---------------------------------------------------------------
+ * What the reference prints to stdout for every message it hands to the tracker unless --quiet is given: displayModesMessage
+ * (mode_s.c:1809-2239, called from track.c:2688-2697), including the line printACASInfoShort adds with a == NULL for DF16 with
+ * MGPU_F_ACAS_RA_VALID (json_out.c:443-629).  Streams, offsets, MGPU_E_OVERFLOW (with *bytes = what the stream needs and nothing
+ * written at or beyond out + cap), n == 0 and the size check are those of mgpu_sbs_encode_ex*; same stream as the gate and the
+ * encoders.  No verdicts: the reference dumps every message.  _device: msgs, fields, reduce_forward, receiver_ids, positions,
+ * decoded_nic, decoded_rc, out and deferred are device pointers; bytes, ndeferred, nskipped host pointers in both forms.
+ *   The message is one whose members are the two records', under the same names: msg, msgbits, correctedbits, score, timestamp,
+ *     sysTimestamp and signalLevel (mgpu_msg_signal_level) from the message record; msgtype (77: Mode A/C) and everything else from the
+ *     field record.  reduce_forward (printed as the int8_t it is), receiverId, decoded_nic and decoded_rc are the caller's arrays;
+ *     cpr_decoded iff positions[i].method is MGPU_CPR_GLOBAL / _LOCAL_RECEIVER / _LOCAL_AIRCRAFT, cpr_relative iff _LOCAL_*; a NULL
+ *     positions array, or any other method: the "CPR decoding:  none" form.  A host tracker vetoes a candidate by clearing `method`.
+ *     Members neither record carries are a memset-0 message's: sbs_in, sbs_pos_valid, mlatEPU, geom_alt_derived and decodeResult are
+ *     0 ("decode: ok"), maybe_addr is 0 — those branches do not exist here (a field record whose addr is HEX_UNKNOWN prints
+ *     " 000000 ?" on its hex line and no address line).  --filter-DF and the debug_* variants are not modelled.
+ *   "CRC:" is mm->crc as mode_s.c:466 leaves it: modesChecksum of raw[] after fixDF17msgtype (fields.msgtype == 17 with another DF in
+ *     raw[0]: the first five bits become 17), over msgbits bits.
+ *   MGPU_DUMP_MLAT: "@%012" PRIX64 prints the WHOLE timestamp (more than 12 digits from 2^48), unlike the raw writer.
+ *   Every %...f is reproduced exactly, in integer arithmetic, from the float promoted to double (or the correctly rounded double
+ *     quotient: timestamp / 12.0, decoded_rc / 1852.0), rounding half to even on the exact binary value.
+ *   Domain — a message that would get a dump but lies outside what the mode prints gets none, no list entry, and adds one to
+ *     *nskipped.  MGPU_DUMP_ONLYADDR: no message.  Every other mode: msgbits other than 56 or 112 (16 for msgtype >= 32): the frame
+ *     line would read past msg[].  Without MGPU_DUMP_RAW also: sysTimestamp outside [0, 253402300800000), timestamp < 0, sig_len == 0,
+ *     a float to be printed (heading, track_rate, roll, gs_selected and gs_v0 / gs_v2 where they differ from it, mach, nav_qnh,
+ *     nav_heading, each under its valid flag) that is not finite or has |x| >= 2^31, a position to be printed (MGPU_F_CPR_VALID and a
+ *     decoded method) with |lat| > 90 or |lon| > 360 or not finite.  A message that gets no dump because of MGPU_DUMP_QUIET is
+ *     counted nowhere.  A dump is at most MGPU_DUMP_MAX = 2599 bytes (proved line by line in dump_format.h).
+ *     Why msgbits belongs to the domain: the reference's frame loop prints msgbits / 8 bytes starting at msg[] and so runs on into
+ *     verbatim[], which these records do not carry, and modesChecksum asserts a whole number of at least three bytes.
+ *   Deferred — "RSSI: %8.1f" of 10 * log10(signalLevel) is the one transcendental, and no device log10 is the host libm's bit for
+ *     bit.  The sign comes from comparing signalLevel with 1.0 (1.0 itself prints 0.0); the magnitude y from the device's double
+ *     log10, and with t = |y| * 10 the rounding is certain iff |t - floor(t) - 0.5| >= 2^-20 (both libraries' errors are a few ulp of a value below 150, about 1e-13).
+ *     An uncertain message (about two per million) is not formatted: it is listed in `deferred` as {index, offset its dump would
+ *     start at} and counted in *ndeferred, with the overflow rule of the SBS list; the stream is exact for "deferred dropped".  The host
+ *     formats those with mgpu_dump_format_host — the same formatter compiled for the host, log10 the host's — and splices the text in
+ *     at the offset.  Nothing is deferred with MGPU_DUMP_ONLYADDR or _RAW.
+ *   fields == NULL, host form only: the library decodes the fields itself; _device: MGPU_E_INVAL. */
+#define MGPU_DUMP_MAX 2599      /* bytes of the longest dump */
+#define MGPU_DUMP_ONLYADDR 1u   /* Modes.onlyaddr: "%06x\n" of addr and nothing else (mode_s.c:1829-1832) */
+#define MGPU_DUMP_RAW      2u   /* Modes.raw: stop after the frame line (:1844-1847) */
+#define MGPU_DUMP_MLAT     4u   /* Modes.mlat: '@' + timestamp instead of '*' when timestamp != 0 (:1835-1839) */
+#define MGPU_DUMP_QUIET    8u   /* Modes.quiet: only messages whose fields.addr == show_only get a dump (track.c:2688-2690) */
+struct mgpu_dump_args {
+    uint32_t size, flags;                    /* sizeof(struct mgpu_dump_args); MGPU_DUMP_* */
+    const struct mgpu_msg *msgs;
+    const struct mgpu_fields *fields;        /* [n]; NULL (host form only): decoded by the library */
+    const uint8_t *reduce_forward;           /* [n] or NULL = 0: mm->reduce_forward, the host tracker's */
+    const uint64_t *receiver_ids;            /* [n] or NULL = 0: mm->receiverId (the "receiverId:" line, sprint_uuid1) */
+    const struct mgpu_position *positions;   /* [n] or NULL: cpr_decoded iff method GLOBAL / LOCAL_*; cpr_relative iff LOCAL_* */
+    const uint8_t  *decoded_nic;             /* [n] or NULL = 0 */
+    const uint32_t *decoded_rc;              /* [n] or NULL = 0 */
+    uint64_t n;
+    uint32_t show_only;                      /* with MGPU_DUMP_QUIET */
+    uint8_t *out; uint64_t cap; uint64_t *bytes;
+    struct mgpu_deferred *deferred; uint64_t deferred_cap;
+    uint64_t *ndeferred, *nskipped;          /* host, out; may be NULL */
+};
+int mgpu_dump_encode_ex(mgpu_ctx *ctx, const struct mgpu_dump_args *args);          /* every array in host memory */
+int mgpu_dump_encode_ex_device(mgpu_ctx *ctx, const struct mgpu_dump_args *args);   /* arrays are device pointers; bytes / ndeferred / nskipped host */
+/* The dump of message `index` of a HOST-memory view of the same arguments (fields must be given; out, cap, bytes, deferred and the
+ * counts are not read), formatted on the host: up to `cap` bytes to `text` (MGPU_DUMP_MAX always suffices), returns the dump's length (0: the message gets none in
+ * this mode), or MGPU_E_INVAL.  Needs no context and no GPU. */
+int64_t mgpu_dump_format_host(const struct mgpu_dump_args *args, uint64_t index, uint8_t *text, uint64_t cap);
+
 /* ---- snip: strip quiet stretches from a UC8 capture (snipMode, readsb.c:1187-1206; `readsb --snip <level>`, :1581-1583) ----------
  *
  * A sample is two bytes (i, q); it is quiet iff abs(i - 127) < level && abs(q - 127) < level in int arithmetic (:1197) — level <= 0:

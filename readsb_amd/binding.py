@@ -187,6 +187,17 @@ class RawArgs(C.Structure):                                           # struct m
                 ("deferred_cap", C.c_uint64), ("ndeferred", C.POINTER(C.c_uint64))]
 
 
+DUMP_ONLYADDR, DUMP_RAW, DUMP_MLAT, DUMP_QUIET = 1, 2, 4, 8             # MGPU_DUMP_*
+DUMP_MAX = 2599                                                       # bytes of a dump (kDumpMax, csrc/dump_format.h)
+
+
+class DumpArgs(C.Structure):                                          # struct mgpu_dump_args
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("msgs", C.c_void_p), ("fields", C.c_void_p), ("reduce_forward", C.c_void_p),
+                ("receiver_ids", C.c_void_p), ("positions", C.c_void_p), ("decoded_nic", C.c_void_p), ("decoded_rc", C.c_void_p), ("n", C.c_uint64),
+                ("show_only", C.c_uint32), ("out", C.c_void_p), ("cap", C.c_uint64), ("bytes", C.POINTER(C.c_uint64)), ("deferred", C.c_void_p),
+                ("deferred_cap", C.c_uint64), ("ndeferred", C.POINTER(C.c_uint64)), ("nskipped", C.POINTER(C.c_uint64))]
+
+
 class SnipArgs(C.Structure):                                          # struct mgpu_snip_args
     _fields_ = [("size", C.c_uint32), ("level", C.c_int32), ("iq", C.c_void_p), ("nsamples", C.c_uint64), ("out", C.c_void_p),
                 ("cap_samples", C.c_uint64), ("nout", C.POINTER(C.c_uint64)), ("quiet_run", C.POINTER(C.c_uint64)), ("pass_samples", C.c_uint64)]
@@ -371,6 +382,10 @@ def load_library():
     lib.mgpu_asterix_encode_ex_device.argtypes = [vp, C.POINTER(AsterixArgs)]
     lib.mgpu_raw_encode_ex.argtypes = [vp, C.POINTER(RawArgs)]
     lib.mgpu_raw_encode_ex_device.argtypes = [vp, C.POINTER(RawArgs)]
+    lib.mgpu_dump_encode_ex.argtypes = [vp, C.POINTER(DumpArgs)]
+    lib.mgpu_dump_encode_ex_device.argtypes = [vp, C.POINTER(DumpArgs)]
+    lib.mgpu_dump_format_host.argtypes = [C.POINTER(DumpArgs), u64, vp, u64]
+    lib.mgpu_dump_format_host.restype = C.c_int64
     lib.mgpu_snip.argtypes = [vp, C.POINTER(SnipArgs)]
     lib.mgpu_snip_device.argtypes = [vp, C.POINTER(SnipArgs)]
     lib.mgpu_merge_by_time.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
@@ -798,6 +813,64 @@ class Demodulator:
                     n, int(now_ms), int(override_squawk), d_out_ptr, cap, C.pointer(nb), d_deferred_ptr, deferred_cap, C.pointer(nd), C.pointer(ns))
         self._chk(self.lib.mgpu_sbs_encode_ex_device(self.ctx, C.byref(a)), "mgpu_sbs_encode_ex_device")
         return int(nb.value), int(nd.value), int(ns.value)
+
+    @staticmethod
+    def _dump_host_args(msgs, flags, fields, reduce_forward, receiver_ids, positions, decoded_nic, decoded_rc, show_only):
+        """-> (struct mgpu_dump_args over host arrays with the output members empty, the arrays it points into)"""
+        msgs = np.ascontiguousarray(msgs)
+        assert msgs.dtype == MSG_DTYPE
+        n = len(msgs)
+
+        def arr(a, dtype):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            assert len(a) == n
+            return a
+        keep = [msgs, arr(fields, FIELDS_DTYPE), arr(reduce_forward, np.uint8), arr(receiver_ids, np.uint64), arr(positions, POSITION_DTYPE),
+                arr(decoded_nic, np.uint8), arr(decoded_rc, np.uint32)]
+        ptr = lambda a: a.ctypes.data if a is not None else None                                     # noqa: E731
+        a = DumpArgs(C.sizeof(DumpArgs), int(flags), *[ptr(k) for k in keep], n, int(show_only))
+        return a, keep
+
+    def dump_encode(self, msgs, flags=0, fields=None, reduce_forward=None, receiver_ids=None, positions=None, decoded_nic=None, decoded_rc=None,
+                    show_only=0, cap=None, deferred_cap=None):
+        """mgpu_dump_encode_ex on host arrays: the decoded-message dumps of a record array, displayModesMessage's bytes
+        (include/modes_gpu.h).  flags: DUMP_*; fields: decode_fields' records or None (decoded by the library); the other arrays are
+        the host tracker's, None = 0.  -> (stream bytes, deferred[] records — the messages whose RSSI rounding is the host's to settle,
+        see dump_format_host — the number of messages outside the printable domain)."""
+        a, keep = self._dump_host_args(msgs, flags, fields, reduce_forward, receiver_ids, positions, decoded_nic, decoded_rc, show_only)
+        n = len(keep[0])
+        cap = int(cap if cap is not None else n * DUMP_MAX + 64)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        dcap = int(deferred_cap if deferred_cap is not None else n)
+        deferred = np.zeros(max(dcap, 1), dtype=DEFERRED_DTYPE)
+        nb, nd, ns = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        a.out, a.cap, a.bytes, a.deferred, a.deferred_cap, a.ndeferred, a.nskipped = out.ctypes.data, cap, C.pointer(nb), deferred.ctypes.data, dcap, C.pointer(nd), \
+            C.pointer(ns)
+        self._chk(self.lib.mgpu_dump_encode_ex(self.ctx, C.byref(a)), "mgpu_dump_encode_ex")
+        return out[: nb.value].tobytes(), deferred[: nd.value].copy(), int(ns.value)
+
+    def dump_encode_device(self, d_msgs_ptr, d_fields_ptr, n, d_out_ptr, cap, flags=0, d_reduce_forward_ptr=None, d_receiver_ids_ptr=None, d_positions_ptr=None,
+                           d_decoded_nic_ptr=None, d_decoded_rc_ptr=None, show_only=0, d_deferred_ptr=None, deferred_cap=0):
+        """mgpu_dump_encode_ex_device: everything in HBM (pointers as ints).  -> (the stream's size in bytes, the number of deferred
+        messages, the number of skipped messages)."""
+        nb, nd, ns = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        a = DumpArgs(C.sizeof(DumpArgs), int(flags), d_msgs_ptr, d_fields_ptr, d_reduce_forward_ptr, d_receiver_ids_ptr, d_positions_ptr, d_decoded_nic_ptr,
+                     d_decoded_rc_ptr, n, int(show_only), d_out_ptr, cap, C.pointer(nb), d_deferred_ptr, deferred_cap, C.pointer(nd), C.pointer(ns))
+        self._chk(self.lib.mgpu_dump_encode_ex_device(self.ctx, C.byref(a)), "mgpu_dump_encode_ex_device")
+        return int(nb.value), int(nd.value), int(ns.value)
+
+    def dump_format_host(self, index, msgs, fields, flags=0, reduce_forward=None, receiver_ids=None, positions=None, decoded_nic=None, decoded_rc=None,
+                         show_only=0):
+        """mgpu_dump_format_host: the dump of message `index` formatted on the host (the host's log10) — the text to splice in at a
+        deferred entry's offset.  -> bytes (empty: the message gets no dump in this mode)."""
+        a, keep = self._dump_host_args(msgs, flags, fields, reduce_forward, receiver_ids, positions, decoded_nic, decoded_rc, show_only)
+        text = np.empty(DUMP_MAX, dtype=np.uint8)
+        k = self.lib.mgpu_dump_format_host(C.byref(a), int(index), text.ctypes.data, DUMP_MAX)
+        if k < 0:
+            raise MgpuError(f"mgpu_dump_format_host: {k}")
+        return text[:k].tobytes()
 
     def asterix_encode(self, msgs, now_ms, fields=None, positions=None, verdict=None, ids=None, ac_baro_alt=None, ac_category=None, remote=False,
                        deferred_cap=None):

@@ -2,6 +2,9 @@
 #include "behind.h"
 
 #include <cmath>
+#include <cstring>
+
+#include "dump_format.h"
 
 extern "C" {
 
@@ -646,6 +649,99 @@ int mgpu_asterix_encode_ex(mgpu_ctx *c, const struct mgpu_asterix_args *a) {
     d.deferred = b.d_deferred.as<mgpu_deferred>();
     if (int rc = asterix_encode_dev(c, d)) return rc;
     return text_out_fetch(c, a->out, *a->bytes, a->deferred, a->verdict ? a->ndeferred : nullptr);
+}
+
+// ---- the decoded-message dump (displayModesMessage, mode_s.c:1809-2239), kernels/dump.inc: the text outputs' workgroup scratch, a length word per message ----
+
+// a: every array a device pointer
+static int dump_encode_dev(mgpu_ctx *c, const struct mgpu_dump_args &a) {
+    Behind &b = *c->behind;
+    const size_t nb = (size_t) (a.n / kBlock + 2);                 // per workgroup: bytes | deferred | skipped, nb entries each
+    if (int rc = b.d_text_blocks.reserve(c, 3 * nb * sizeof(uint32_t))) return rc;
+    if (int rc = b.d_text_off.reserve(c, 3 * nb * sizeof(unsigned long long))) return rc;
+    if (int rc = b.d_text_total.reserve_exact(c, 4 * sizeof(unsigned long long))) return rc;
+    if (int rc = b.d_dump_len.reserve(c, a.n * sizeof(uint32_t))) return rc;
+    const DumpScratch w = {b.d_dump_len.as<uint32_t>(), b.d_text_blocks.as<uint32_t>(), b.d_text_off.as<unsigned long long>(), b.d_text_total.as<unsigned long long>(), nb};
+    const DumpParams p = {a.msgs, a.fields, a.reduce_forward, (const unsigned long long *) a.receiver_ids, a.positions, a.decoded_nic, a.decoded_rc, a.flags, a.show_only};
+    launch_dump_encode(p, a.n, w, a.out, a.cap, a.deferred, a.deferred_cap, c->stream_aux);
+    const TextScratch t = {nullptr, w.blocks, w.off, w.total, nb};
+    return text_finish(c, t, true, a.cap, a.deferred_cap, a.bytes, a.ndeferred, a.nskipped, true);
+}
+
+static bool dump_args_ok(const struct mgpu_dump_args *a, bool device) {
+    if (!a || a->size < sizeof(struct mgpu_dump_args) || !a->bytes) return false;
+    if (a->flags & ~(MGPU_DUMP_ONLYADDR | MGPU_DUMP_RAW | MGPU_DUMP_MLAT | MGPU_DUMP_QUIET)) return false;
+    if (a->n && (!a->msgs || (device && !a->fields))) return false;
+    if ((a->cap && !a->out) || (a->deferred_cap && !a->deferred)) return false;
+    return true;
+}
+
+int mgpu_dump_encode_ex_device(mgpu_ctx *c, const struct mgpu_dump_args *a) {
+    if (!c || !dump_args_ok(a, true)) return MGPU_E_INVAL;
+    *a->bytes = 0;
+    if (a->ndeferred) *a->ndeferred = 0;
+    if (a->nskipped) *a->nskipped = 0;
+    if (a->n == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return dump_encode_dev(c, *a);
+}
+
+int mgpu_dump_encode_ex(mgpu_ctx *c, const struct mgpu_dump_args *a) {
+    if (!c || !dump_args_ok(a, false)) return MGPU_E_INVAL;
+    *a->bytes = 0;
+    if (a->ndeferred) *a->ndeferred = 0;
+    if (a->nskipped) *a->nskipped = 0;
+    const uint64_t n = a->n;
+    if (n == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    Behind &b = *c->behind;
+    struct mgpu_dump_args d = *a;
+    if (a->fields) {
+        if (int rc = stage_messages(c, a->msgs, n)) return rc;
+        if (int rc = b.d_fields.reserve(c, n * sizeof(mgpu_fields))) return rc;
+        HIPCHK(c, hipMemcpyAsync(b.d_fields.p, a->fields, n * sizeof(mgpu_fields), hipMemcpyHostToDevice, c->stream_aux));
+    } else if (int rc = fields_staged(c, a->msgs, n)) return rc;
+    d.msgs = b.d_beast_in.as<mgpu_msg>();
+    d.fields = b.d_fields.as<mgpu_fields>();
+    const void *d_rf, *d_ids, *d_pos, *d_nic, *d_rc;
+    if (int rc = asterix_stage(c, b.d_dump_forward, a->reduce_forward, n, &d_rf)) return rc;
+    if (int rc = asterix_stage(c, b.d_dump_ids, a->receiver_ids, n * sizeof(uint64_t), &d_ids)) return rc;
+    if (int rc = asterix_stage(c, b.d_dump_pos, a->positions, n * sizeof(mgpu_position), &d_pos)) return rc;
+    if (int rc = asterix_stage(c, b.d_dump_nic, a->decoded_nic, n, &d_nic)) return rc;
+    if (int rc = asterix_stage(c, b.d_dump_rc, a->decoded_rc, n * sizeof(uint32_t), &d_rc)) return rc;
+    d.reduce_forward = (const uint8_t *) d_rf;
+    d.receiver_ids = (const uint64_t *) d_ids;
+    d.positions = (const mgpu_position *) d_pos;
+    d.decoded_nic = (const uint8_t *) d_nic;
+    d.decoded_rc = (const uint32_t *) d_rc;
+    if (int rc = text_out_reserve(c, a->cap, true, a->deferred_cap)) return rc;
+    d.out = b.d_beast_out.as<uint8_t>();
+    d.deferred = b.d_deferred.as<mgpu_deferred>();
+    uint64_t nd = 0;
+    d.ndeferred = &nd;
+    const int rc = dump_encode_dev(c, d);
+    if (a->ndeferred) *a->ndeferred = nd;
+    if (rc) return rc;
+    return text_out_fetch(c, a->out, *a->bytes, a->deferred, &nd);
+}
+
+// the same formatter on the host, where log10 is the host libm's: no context, no GPU
+int64_t mgpu_dump_format_host(const struct mgpu_dump_args *a, uint64_t index, uint8_t *text, uint64_t cap) {
+    if (!a || a->size < sizeof(struct mgpu_dump_args) || !a->msgs || !a->fields || index >= a->n || (cap && !text)) return MGPU_E_INVAL;
+    if (a->flags & ~(MGPU_DUMP_ONLYADDR | MGPU_DUMP_RAW | MGPU_DUMP_MLAT | MGPU_DUMP_QUIET)) return MGPU_E_INVAL;
+    const DumpIn in = {a->msgs + index, a->fields + index, a->positions ? a->positions + index : nullptr, a->receiver_ids ? a->receiver_ids[index] : 0ull,
+                       a->decoded_rc ? a->decoded_rc[index] : 0u, a->reduce_forward ? a->reduce_forward[index] : (uint8_t) 0,
+                       a->decoded_nic ? a->decoded_nic[index] : (uint8_t) 0};
+    if (dump_classify(in, a->flags, a->show_only, true) != DUMP_LINE) return 0;
+    DumpCountSink count = {0};
+    dump_format(in, a->flags, true, count);
+    if (count.n > (uint32_t) kDumpMax) return MGPU_E_INVAL;      // (the bound is proved in dump_format.h; never trust a proof with a stack buffer)
+    uint8_t buf[kDumpMax];
+    DumpByteSink s = {buf};
+    dump_format(in, a->flags, true, s);
+    const uint64_t len = (uint64_t) (s.p - buf);
+    if (cap) memcpy(text, buf, len < cap ? len : cap);
+    return (int64_t) len;
 }
 
 uint32_t mgpu_crc_checksum(const uint8_t *msg, int bits) { return crc_tables().checksum(msg, bits); }

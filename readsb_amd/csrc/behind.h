@@ -39,6 +39,9 @@ struct Behind {
     // runs each); the three totals; the host-array forms' positions and geom_delta values (the rest is staged where the encoder stages it)
     DevBuf d_text_len, d_text_blocks, d_text_off, d_text_total, d_text_pos, d_text_delta;
     DevBuf d_asx_ids, d_asx_baro_alt, d_asx_category;            // mgpu_asterix_encode_ex's three optional arrays
+    // the message dump (kernels/dump.inc): per message a dump's length (32 bits; the workgroup scratch is the text outputs'); the host-array
+    // form's five optional arrays
+    DevBuf d_dump_len, d_dump_forward, d_dump_ids, d_dump_pos, d_dump_nic, d_dump_rc;
     DevBuf d_fields;                                         // the host-array forms' field records
     DevBuf d_roll_tan;                                       // tables.h build_roll_tangent_table(), uploaded on first use
     // the first-stage tracking gate (kernels/gate.inc): the aircraft table (1 GiB, allocated and zeroed by the first call), its scratch,

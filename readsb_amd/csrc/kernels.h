@@ -249,6 +249,26 @@ struct TextAsterixParams {
 };
 void launch_asterix_encode(const TextAsterixParams &a, uint64_t n, const TextScratch &w, uint8_t *out, uint64_t cap, mgpu_deferred *deferred, uint64_t def_cap,
                            hipStream_t s);
+// the decoded-message dump (kernels/dump.inc; displayModesMessage, mode_s.c:1809-2239): the passes of the text outputs with a write pass of its own
+struct DumpParams {
+    const mgpu_msg *msgs;
+    const mgpu_fields *fields;
+    const uint8_t *reduce_forward;    // the five optional arrays: null where modes_gpu.h allows it
+    const unsigned long long *receiver_ids;
+    const mgpu_position *positions;
+    const uint8_t *decoded_nic;
+    const uint32_t *decoded_rc;
+    uint32_t flags;                   // MGPU_DUMP_*
+    uint32_t show_only;
+};
+struct DumpScratch {
+    uint32_t *meta;                   // [n] a dump's length, or the deferred mark
+    uint32_t *blocks;                 // [3 * stride] per workgroup: bytes | deferred messages | skipped messages
+    unsigned long long *off;          // [3 * stride] the exclusive prefix sums of the first two
+    unsigned long long *total;        // [3] the totals
+    size_t stride;                    // >= ceil(n / kBlock)
+};
+void launch_dump_encode(const DumpParams &a, uint64_t n, const DumpScratch &w, uint8_t *out, uint64_t cap, mgpu_deferred *deferred, uint64_t def_cap, hipStream_t s);
 // `readsb --snip` over UC8 samples (kernels/snip.inc; snipMode, readsb.c:1187-1206)
 constexpr uint64_t kSnipTileSamples = 8192;   // samples per tile of its passes, and per workgroup: consecutive tiles
 constexpr uint64_t kSnipGroupSamples = 4 * kSnipTileSamples;

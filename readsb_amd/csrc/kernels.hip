@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "tables.h"
 #include "snip_mask.h"
+#include "dump_format.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -127,6 +128,7 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 #include "kernels/beast.inc"
 #include "kernels/text.inc"
 #include "kernels/asterix.inc"
+#include "kernels/dump.inc"
 #include "kernels/snip.inc"
 #include "kernels/fields.inc"
 #include "kernels/gate.inc"

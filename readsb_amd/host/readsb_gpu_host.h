@@ -88,6 +88,13 @@ int gpu_ifile_run_until(struct gpu_demod *g, int fd, input_format_t format, unsi
 struct gpu_sbs_opts { const char *path; int64_t now_ms; int have_ref, gnss; double lat, lon; int asterix; };
 int gpu_sbs_run(mgpu_ctx *ctx, int fd, input_format_t format, unsigned chunk_buffers, const struct gpu_sbs_opts *o, struct mgpu_counters *counters);
 
+/* readsb_gpu_ifile --dump-out (dump_gpu.c): the resident chain ending in mgpu_dump_encode_ex_device — feed, field decode, dump encoder —
+ * and `path` receives what displayModesMessage prints for the capture (mode_s.c:1809-2239).  The few messages the device defers (the
+ * RSSI line's log10 is the host's to round) are formatted by mgpu_dump_format_host and spliced in: the file is complete.  No tracker
+ * runs, so reduce_forward prints 0 and every CPR block says "decoding: none".  flags: MGPU_DUMP_*; show_only with MGPU_DUMP_QUIET. */
+struct gpu_dump_opts { const char *path; uint32_t flags, show_only; };
+int gpu_dump_run(mgpu_ctx *ctx, int fd, input_format_t format, unsigned chunk_buffers, const struct gpu_dump_opts *o, struct mgpu_counters *counters);
+
 /* readsb_gpu_ifile --snip LEVEL (snip_gpu.c): `readsb --snip <level>` (snipMode, readsb.c:1187-1206) through mgpu_snip — the UC8 bytes
  * of `fd` with every quiet stretch cut down to its first 32 samples, to stdout.  cfg: the device to use.  0 or a negative MGPU_E_* code. */
 int gpu_snip_run(const struct mgpu_config *cfg, int fd, int level);

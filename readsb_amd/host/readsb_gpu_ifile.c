@@ -5,6 +5,8 @@
  * --sbs-out PATH: instead of the raw lines, the BaseStation feed of the capture (modesSendSBSOutput, net_io.c:3184-3404) into PATH,
  * with nothing but the text leaving the GPU: feed -> field decode -> tracking gate -> position decode -> SBS encoder (sbs_gpu.c).
  * --asterix-out PATH: the same chain ending in the ASTERIX CAT021 encoder (modesSendAsterixOutput, net_io.c:2416-2945).
+ * --dump-out PATH: the decoded-message dump of the capture — what the reference prints to stdout without --quiet (displayModesMessage,
+ * mode_s.c:1809-2239) — into PATH by the resident chain feed -> field decode -> dump encoder (dump_gpu.c).
  * --snip LEVEL: `readsb --snip <level>` (snipMode, readsb.c:1187-1206) instead of demodulating: stdin (or --ifile) to stdout (snip_gpu.c).
  */
 #include <fcntl.h>
@@ -36,6 +38,7 @@ static const char usage[] =
     "                 [--preamble-threshold N] [--gpu-device N] [--gpu-chunk-buffers N] [--startup-time-ms MS] [--stats] [--raw --mlat]\n"
     "                 [--sbs-out PATH [--sbs-now-ms MS] [--lat DEG --lon DEG] [--gnss]]\n"
     "                 [--asterix-out PATH [--asterix-now-ms MS] [--lat DEG --lon DEG]]\n"
+    "                 [--dump-out PATH [--raw] [--mlat] [--dump-onlyaddr] [--show-only HEX]]\n"
     "readsb_gpu_ifile --snip LEVEL [--ifile PATH|-] [--gpu-device N]\n"
     "  default: one `@<timestamp><frame>;` line per accepted message on stdout (readsb --raw --mlat)\n"
     "  --sbs-out PATH   write the BaseStation (port 30003) lines of the capture to PATH instead; the messages, their field records,\n"
@@ -46,6 +49,11 @@ static const char usage[] =
     "  --asterix-out PATH  write the ASTERIX CAT021 target reports of the capture (the asterix_out connector's stream) to PATH instead,\n"
     "                   by the same resident chain; deferred messages are DROPPED likewise.  No receiver ids, fresh aircraft state.\n"
     "  --asterix-now-ms MS  the clock of I021/077 and of the day's midnight (ms since 1970; default: the clock when the program starts)\n"
+    "  --dump-out PATH  write the decoded-message dump of every message (what readsb prints to stdout without --quiet) to PATH instead,\n"
+    "                   formatted on the GPU; --raw, --mlat and --dump-onlyaddr select readsb's modes of that output (only here: the\n"
+    "                   default output stays the --raw --mlat line), --show-only HEX keeps the messages of one address.  No tracker\n"
+    "                   runs, so the file equals the reference program's stdout EXCEPT that `reduce_forward:` always prints 0 and\n"
+    "                   every CPR block has the `CPR decoding:  none` form (no decoded position, NIC or Rc lines).  Not with --modeac.\n"
     "  --lat, --lon     the receiver's location (enables positions relative to the receiver and surface positions)\n"
     "  --gnss           Modes.use_gnss: geometric altitudes and rates with the H suffix where available\n"
     "  --snip LEVEL     readsb --snip: copy UC8 samples from stdin (or --ifile PATH) to stdout, every stretch of samples with\n"
@@ -53,6 +61,8 @@ static const char usage[] =
 
 /* readsb_amd/host/sbs_gpu.c; absent from builds against a stand-in library, which have no device to keep anything on */
 #pragma weak gpu_sbs_run
+/* readsb_amd/host/dump_gpu.c; absent likewise */
+#pragma weak gpu_dump_run
 /* readsb_amd/host/snip_gpu.c; absent likewise (a stand-in library has no mgpu_snip) */
 #pragma weak gpu_snip_run
 
@@ -64,6 +74,7 @@ int main(int argc, char **argv) {
     int stats = 0;
     unsigned chunk = 256;
     struct gpu_sbs_opts sbs = {NULL, -1, 0, 0, 0.0, 0.0, 0};
+    struct gpu_dump_opts dump = {NULL, 0, 0};
     int have_lat = 0, have_lon = 0, snip = 0, snip_level = 0;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--ifile") && i + 1 < argc) ifile = argv[++i];
@@ -88,7 +99,12 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--gnss")) sbs.gnss = 1;
         else if (!strcmp(argv[i], "--snip") && i + 1 < argc) { snip = 1; snip_level = atoi(argv[++i]); }     /* readsb.c:1581-1583 */
         else if (!strcmp(argv[i], "--help")) { fputs(usage, stdout); return 0; }
-        else if (!strcmp(argv[i], "--raw") || !strcmp(argv[i], "--mlat") || !strcmp(argv[i], "--quiet")) { }
+        else if (!strcmp(argv[i], "--dump-out") && i + 1 < argc) dump.path = argv[++i];
+        else if (!strcmp(argv[i], "--dump-onlyaddr")) dump.flags |= MGPU_DUMP_ONLYADDR;
+        else if (!strcmp(argv[i], "--show-only") && i + 1 < argc) { dump.show_only = (uint32_t) strtoul(argv[++i], NULL, 16); dump.flags |= MGPU_DUMP_QUIET; }
+        else if (!strcmp(argv[i], "--raw")) dump.flags |= MGPU_DUMP_RAW;          /* (read with --dump-out only) */
+        else if (!strcmp(argv[i], "--mlat")) dump.flags |= MGPU_DUMP_MLAT;
+        else if (!strcmp(argv[i], "--quiet")) { }
         else if (!strcmp(argv[i], "--device-type") && i + 1 < argc) ++i;
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
@@ -103,6 +119,8 @@ int main(int argc, char **argv) {
     sbs.have_ref = have_lat && have_lon;
     if (sbs.path && !gpu_sbs_run) { fprintf(stderr, "--sbs-out / --asterix-out: this build has no GPU chain\n"); return 2; }
     if (sbs.path && cfg.mode_ac) { fprintf(stderr, "--sbs-out / --asterix-out: not with --modeac (its replies are merged on the host)\n"); return 2; }
+    if (dump.path && !gpu_dump_run) { fprintf(stderr, "--dump-out: this build has no GPU chain\n"); return 2; }
+    if (dump.path && (cfg.mode_ac || sbs.path)) { fprintf(stderr, "--dump-out: not with --modeac, --sbs-out or --asterix-out\n"); return 2; }
     if (sbs.path && sbs.now_ms < 0) {
         struct timespec ts;
         clock_gettime(CLOCK_REALTIME, &ts);
@@ -115,8 +133,9 @@ int main(int argc, char **argv) {
     cfg.max_samples = (uint64_t) chunk * 131072;
     struct gpu_demod g;
     if (gpu_demod_open(&g, &cfg, print_raw, stdout) != MGPU_OK) return 1;
-    int rc = sbs.path ? gpu_sbs_run(g.ctx, fd, fmt, chunk, &sbs, &g.counters) : gpu_ifile_run(&g, fd, fmt, chunk);
-    if (rc != MGPU_OK && !sbs.path) fprintf(stderr, "gpu_ifile_run: %s (%s)\n", mgpu_strerror(rc), mgpu_last_error(g.ctx));
+    int rc = dump.path ? gpu_dump_run(g.ctx, fd, fmt, chunk, &dump, &g.counters)
+             : sbs.path ? gpu_sbs_run(g.ctx, fd, fmt, chunk, &sbs, &g.counters) : gpu_ifile_run(&g, fd, fmt, chunk);
+    if (rc != MGPU_OK && !sbs.path && !dump.path) fprintf(stderr, "gpu_ifile_run: %s (%s)\n", mgpu_strerror(rc), mgpu_last_error(g.ctx));
     fflush(stdout);
     if (stats && rc == MGPU_OK) {
         const struct mgpu_counters *c = &g.counters;
