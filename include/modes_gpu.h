@@ -1034,6 +1034,70 @@ struct mgpu_snip_args {
 int mgpu_snip(mgpu_ctx *ctx, const struct mgpu_snip_args *args);
 int mgpu_snip_device(mgpu_ctx *ctx, const struct mgpu_snip_args *args);
 
+/* ---- UAT input: uat2esnt over a stream of dump978 downlink lines (`--net-uat-in-port`; decodeUatMessage, net_io.c:4334-4372 ->
+ *      uat2esnt_convert_message, uat2esnt/uat2esnt.c:823, uat2esnt/uat_decode.c) -----------------------------------------------------
+ *
+ * text is a byte stream.  A line is the bytes between two '\n'; bytes behind the last '\n' are not consumed: *consumed says how many
+ * were, and the caller carries the rest into its next call, as readsb's client buffer does.  Within a line a NUL ends the content
+ * (strlen, net_io.c:4337); a trailing '\r' is ordinary content.  Every line gives zero to four DF18 extended squitters, each an AVR
+ * line of 45 bytes, "<FF004D4C4155" + two hex digits of the signal byte + 28 hex digits + ";\n", in the reference's order; out gets
+ * them in line order.  Per frame, in the same order and optionally: msgs (the record decodeHexMessage + decodeModesMessage leave:
+ * timestamp 0xFF004D4C4155, sysTimestamp now_ms, msgtype 18, msgbits 112, correctedbits 0, score 0, phase 0, addr = AA, msg == raw
+ * = the frame, sig_sumsq = (257 * sig)^2 with sig_len 1), sig (the signal byte) and line_of (the index of the source line, counted
+ * from the start of this call's text); msgs_cap entries each.
+ *   With that sig_sumsq mgpu_msg_signal_level differs from the reference's (sig / 255.0)^2 in the last bits for 126 of the 256 byte
+ *     values (evaluated on the CPU); the signal byte the beast encoder recomputes from it equals sig for all 256.  The exact byte is
+ *     in the sig array.
+ *   The signal byte (generate_esnt, uat2esnt.c:684-691) of an ss= / rssi= value in the simple form [+-]?[0-9]{1,3}(\.[0-9])? followed
+ *     by ';' or the end of the line — the %.1f dump978 prints — comes from a table the library builds once with the host's sscanf and
+ *     libm.  A '-' line with an ss= / rssi= field in another form where the reference's walk reads it, or longer than 256 bytes, is
+ *     DEFERRED: nothing is written for it, its index is listed in `deferred` (ascending; *ndeferred of them), and
+ *     mgpu_uat_format_host gives its frames, which belong in front of the first frame whose line_of is larger.
+ *   A documented departure: a downlink line whose payload has fewer bytes than the decoders of its MDB type read (types 0, 4, 7-10:
+ *     17; 3: 27; 1, 2, 5, 6: 31; 11-31: 4) produces nothing and is counted in *nshort; the reference ignores the length
+ *     (frame_to_esnt, uat2esnt.c:716) and decodes uninitialised stack.  (A deferred line is not counted, whatever the host finds.)
+ *   Not modelled: replayUatMsg (net_io.c:4341); the "ignore the first UAT message of an aircraft for 300 s" rule (:4357-4366), which
+ *     belongs to the aircraft table; use_tisb = 0 (the reference never clears it); uplink frames ('+' lines: never any output).
+ *   args->size smaller than sizeof(struct mgpu_uat_args), a NULL ctx, args, bytes, consumed, nlines or nframes, text NULL with
+ *     nbytes != 0, out NULL with cap != 0, deferred or ndeferred NULL with deferred_cap != 0, out overlapping text: MGPU_E_INVAL.  nbytes == 0: MGPU_OK with zeros.  More text than cap, more frames than msgs_cap (where msgs, sig or line_of
+ *     is given) or more deferred lines than deferred_cap: MGPU_E_OVERFLOW with *bytes, *nframes and *ndeferred = what is needed;
+ *     nothing is stored at or beyond any capacity.
+ *   mgpu_uat_encode: every array in host memory; the text goes through the library's device scratch in passes of pass_bytes bytes
+ *     (0: the library's default) cut at line ends, so it may be larger than the device's memory.
+ *   mgpu_uat_encode_device: text, out, msgs, sig, line_of device pointers (no alignment asked of any); the counters and the deferred
+ *     list are in host memory in both forms.  nbytes < 2^32 * 8192 / 2.  pass_bytes is ignored. */
+struct mgpu_uat_args {
+    uint32_t size;                     /* sizeof(struct mgpu_uat_args) */
+    uint32_t reserved;                 /* 0 */
+    const uint8_t *text;
+    uint64_t nbytes;
+    uint8_t *out;                      /* cap bytes; must not overlap text */
+    uint64_t cap;
+    struct mgpu_msg *msgs;             /* optional, msgs_cap entries: one record per frame */
+    uint8_t *sig;                      /* optional, msgs_cap entries: the signal byte per frame */
+    uint64_t *line_of;                 /* optional, msgs_cap entries: the source line per frame */
+    uint64_t msgs_cap;
+    uint64_t *deferred;                /* host, deferred_cap entries: the indices of the deferred lines */
+    uint64_t deferred_cap;
+    int64_t now_ms;                    /* the records' sysTimestamp */
+    uint64_t *bytes;                   /* host, out: bytes of text written = 45 * *nframes */
+    uint64_t *consumed;                /* host, out: bytes of text up to and including the last '\n' */
+    uint64_t *nlines;                  /* host, out: lines in them */
+    uint64_t *nframes;                 /* host, out */
+    uint64_t *nshort;                  /* host, out, optional */
+    uint64_t *ndeferred;               /* host, out, optional (required with deferred_cap != 0) */
+    uint64_t pass_bytes;               /* host form: bytes staged per pass; 0 = the library's default */
+};
+int mgpu_uat_encode(mgpu_ctx *ctx, const struct mgpu_uat_args *args);
+int mgpu_uat_encode_device(mgpu_ctx *ctx, const struct mgpu_uat_args *args);
+/* Line `line_index` of a HOST-memory text (args->text, args->nbytes, args->now_ms; nothing else of args is read), formatted on the
+ * host with nothing deferred: up to `cap` bytes of its AVR lines to `text` (180 always suffice), and — where not NULL — its records
+ * to msgs[0..4) and its signal byte to *sig.  Returns the number of bytes (45 per frame; 0: the line gives nothing), or MGPU_E_INVAL
+ * (args, a line that does not exist).  Needs no context and no GPU. */
+int64_t mgpu_uat_format_host(const struct mgpu_uat_args *args, uint64_t line_index, uint8_t *text, uint64_t cap, struct mgpu_msg *msgs, uint8_t *sig);
+/* The same for a line given by its bytes (without the '\n'). */
+int64_t mgpu_uat_format_line_host(const uint8_t *line, uint64_t len, int64_t now_ms, uint8_t *text, uint64_t cap, struct mgpu_msg *msgs, uint8_t *sig);
+
 /* ---- tables, for known-answer tests against crc.c --------------------------------- */
 
 /* These run on the host (they are how the device tables are built) and need no context. */

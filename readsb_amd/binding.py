@@ -203,6 +203,16 @@ class SnipArgs(C.Structure):                                          # struct m
                 ("cap_samples", C.c_uint64), ("nout", C.POINTER(C.c_uint64)), ("quiet_run", C.POINTER(C.c_uint64)), ("pass_samples", C.c_uint64)]
 
 
+class UatArgs(C.Structure):                                           # struct mgpu_uat_args
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_uint32), ("text", C.c_void_p), ("nbytes", C.c_uint64), ("out", C.c_void_p), ("cap", C.c_uint64),
+                ("msgs", C.c_void_p), ("sig", C.c_void_p), ("line_of", C.c_void_p), ("msgs_cap", C.c_uint64), ("deferred", C.c_void_p), ("deferred_cap", C.c_uint64),
+                ("now_ms", C.c_int64), ("bytes", C.POINTER(C.c_uint64)), ("consumed", C.POINTER(C.c_uint64)), ("nlines", C.POINTER(C.c_uint64)),
+                ("nframes", C.POINTER(C.c_uint64)), ("nshort", C.POINTER(C.c_uint64)), ("ndeferred", C.POINTER(C.c_uint64)), ("pass_bytes", C.c_uint64)]
+
+
+UAT_FRAME_TEXT = 45                         # bytes of one AVR line of mgpu_uat_encode
+
+
 ABI_VERSION = 6                             # MGPU_ABI_VERSION of the include/modes_gpu.h these ctypes mirrors were written against
 
 
@@ -386,6 +396,12 @@ def load_library():
     lib.mgpu_dump_encode_ex_device.argtypes = [vp, C.POINTER(DumpArgs)]
     lib.mgpu_dump_format_host.argtypes = [C.POINTER(DumpArgs), u64, vp, u64]
     lib.mgpu_dump_format_host.restype = C.c_int64
+    lib.mgpu_uat_encode.argtypes = [vp, C.POINTER(UatArgs)]
+    lib.mgpu_uat_encode_device.argtypes = [vp, C.POINTER(UatArgs)]
+    lib.mgpu_uat_format_host.argtypes = [C.POINTER(UatArgs), u64, vp, u64, vp, vp]
+    lib.mgpu_uat_format_host.restype = C.c_int64
+    lib.mgpu_uat_format_line_host.argtypes = [vp, u64, C.c_int64, vp, u64, vp, vp]
+    lib.mgpu_uat_format_line_host.restype = C.c_int64
     lib.mgpu_snip.argtypes = [vp, C.POINTER(SnipArgs)]
     lib.mgpu_snip_device.argtypes = [vp, C.POINTER(SnipArgs)]
     lib.mgpu_merge_by_time.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
@@ -964,6 +980,44 @@ class Demodulator:
         a = SnipArgs(C.sizeof(SnipArgs), int(level), d_iq_ptr, int(nsamples), d_out_ptr, int(cap_samples), C.pointer(nout), C.pointer(run), 0)
         self._chk(self.lib.mgpu_snip_device(self.ctx, C.byref(a)), "mgpu_snip_device")
         return int(nout.value), int(run.value)
+
+    def uat_encode(self, text, now_ms=0, settle=True, pass_bytes=0):
+        """mgpu_uat_encode on a host byte string of dump978 lines (`--net-uat-in-port`): every downlink line to its DF18 extended
+        squitters as AVR lines, the reference's uat2esnt byte for byte.  settle: the lines the device defers (a signal value outside
+        dump978's %.1f form, a line longer than 256 bytes) are formatted on the host (mgpu_uat_format_host) and put where they belong;
+        otherwise they are left out and listed.  -> dict(text, msgs, sig, line_of, consumed, nlines, nshort, deferred)."""
+        buf = np.frombuffer(bytes(text), dtype=np.uint8)
+        most = buf.size * 4 // 37 + 4                       # at most 4 frames per 37 bytes of text (uat_format.h)
+        out = np.empty(most * UAT_FRAME_TEXT, dtype=np.uint8)
+        msgs, sig, line_of = np.zeros(most, dtype=MSG_DTYPE), np.empty(most, dtype=np.uint8), np.empty(most, dtype=np.uint64)
+        deferred = np.empty(buf.size // 14 + 1, dtype=np.uint64)     # a deferred line has 14 bytes at least
+        c = [C.c_uint64(0) for _ in range(6)]
+        a = UatArgs(C.sizeof(UatArgs), 0, buf.ctypes.data if buf.size else None, buf.size, out.ctypes.data, out.size, msgs.ctypes.data, sig.ctypes.data,
+                    line_of.ctypes.data, most, deferred.ctypes.data, deferred.size, int(now_ms), *[C.pointer(x) for x in c], int(pass_bytes))
+        self._chk(self.lib.mgpu_uat_encode(self.ctx, C.byref(a)), "mgpu_uat_encode")
+        nbytes, consumed, nlines, nframes, nshort, ndef = (int(x.value) for x in c)
+        res = dict(text=out[:nbytes].tobytes(), msgs=msgs[:nframes].copy(), sig=sig[:nframes].copy(), line_of=line_of[:nframes].copy(), consumed=consumed,
+                   nlines=nlines, nshort=nshort, deferred=deferred[:ndef].copy())
+        if settle and ndef:
+            parts, recs, sigs, lines, at = [], [], [], [], 0
+            line_buf, rec_buf, sig_buf = np.empty(4 * UAT_FRAME_TEXT, dtype=np.uint8), np.zeros(4, dtype=MSG_DTYPE), C.c_uint8(0)
+
+            def take(upto):
+                nonlocal at
+                parts.append(res["text"][at * UAT_FRAME_TEXT: upto * UAT_FRAME_TEXT])
+                recs.append(res["msgs"][at:upto]); sigs.append(res["sig"][at:upto]); lines.append(res["line_of"][at:upto])
+                at = upto
+            for index in res["deferred"].tolist():
+                take(int(np.searchsorted(res["line_of"], index)))
+                n = int(self.lib.mgpu_uat_format_host(C.byref(a), index, line_buf.ctypes.data, line_buf.size, rec_buf.ctypes.data, C.addressof(sig_buf)))
+                if n < 0:
+                    raise MgpuError(f"mgpu_uat_format_host failed ({n})")
+                k = n // UAT_FRAME_TEXT
+                parts.append(line_buf[:n].tobytes())
+                recs.append(rec_buf[:k].copy()); sigs.append(np.full(k, sig_buf.value, dtype=np.uint8)); lines.append(np.full(k, index, dtype=np.uint64))
+            take(nframes)
+            res.update(text=b"".join(parts), msgs=np.concatenate(recs), sig=np.concatenate(sigs), line_of=np.concatenate(lines))
+        return res
 
     def merge_by_time(self, lists, ids=None, verdicts=None):
         """mgpu_merge_by_time on host arrays: the receivers' lists merged by timestamp on the GPU, equal stamps in input order —

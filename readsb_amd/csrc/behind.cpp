@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "dump_format.h"
+#include "uat_format.h"
 
 extern "C" {
 
@@ -742,6 +743,127 @@ int64_t mgpu_dump_format_host(const struct mgpu_dump_args *a, uint64_t index, ui
     const uint64_t len = (uint64_t) (s.p - buf);
     if (cap) memcpy(text, buf, len < cap ? len : cap);
     return (int64_t) len;
+}
+
+// ---- UAT input: uat2esnt over dump978 downlink lines (uat_format.h, kernels/uat.inc) ----
+
+struct UatCounts { uint64_t lines, consumed, frames, deferred, nshort; };
+
+// a: text, out and the three per-frame arrays device pointers; a.deferred a HOST array.  The counts of this text; the deferred lines'
+// indices (line_base added) to a.deferred[listed ..] as far as deferred_cap reaches.  Overflows are the caller's to judge.
+static int uat_encode_dev(mgpu_ctx *c, const struct mgpu_uat_args &a, uint64_t line_base, uint64_t listed, UatCounts *n) {
+    Behind &b = *c->behind;
+    if (!b.d_uat_sig_table.p) {
+        if (int rc = b.d_uat_sig_table.reserve_exact(c, kUatSigTable)) return rc;
+        HIPCHK(c, hipMemcpy(b.d_uat_sig_table.p, uat_sig_table(), kUatSigTable, hipMemcpyHostToDevice));
+    }
+    const size_t nb = (size_t) (a.nbytes / kUatTile + 2);
+    const uint64_t def_room = std::min<uint64_t>(a.deferred_cap > listed ? a.deferred_cap - listed : 0, uat_max_deferred(a.nbytes));   // (no more than the text can defer)
+    if (int rc = b.d_uat_meta.reserve(c, nb * kBlock * sizeof(uint16_t))) return rc;
+    if (int rc = b.d_uat_blocks.reserve(c, 5 * nb * sizeof(uint32_t))) return rc;
+    if (int rc = b.d_uat_off.reserve(c, 3 * nb * sizeof(unsigned long long))) return rc;
+    if (int rc = b.d_uat_total.reserve_exact(c, 8 * sizeof(unsigned long long))) return rc;
+    if (int rc = b.d_uat_deferred.reserve(c, (def_room + 64) * sizeof(unsigned long long))) return rc;
+    const UatScratch w = {b.d_uat_meta.as<uint16_t>(), b.d_uat_blocks.as<uint32_t>(), b.d_uat_off.as<unsigned long long>(), b.d_uat_total.as<unsigned long long>(), nb};
+    const bool records = a.msgs || a.sig || a.line_of;
+    const UatParams p = {a.text, a.nbytes, b.d_uat_sig_table.as<uint8_t>(), a.out, a.cap, a.msgs, a.sig, (unsigned long long *) a.line_of, records ? a.msgs_cap : 0,
+                         b.d_uat_deferred.as<unsigned long long>(), def_room, line_base, a.now_ms};
+    launch_uat_encode(p, w, c->stream_aux);
+    HIPCHK(c, hipGetLastError());
+    unsigned long long total[5] = {0, 0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(total, w.total, sizeof total, hipMemcpyDeviceToHost, c->stream_aux));
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    *n = {total[0], total[1], total[2], total[3], total[4]};
+    const uint64_t fetch = std::min<uint64_t>(total[3], def_room);
+    if (fetch) HIPCHK(c, hipMemcpy(a.deferred + listed, b.d_uat_deferred.p, fetch * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return MGPU_OK;
+}
+
+static bool uat_args_ok(const struct mgpu_uat_args *a) {
+    if (!a || a->size < sizeof(struct mgpu_uat_args) || !a->bytes || !a->consumed || !a->nlines || !a->nframes) return false;
+    if (a->nbytes > kUatMaxBytes || a->cap > UINT64_MAX / 2) return false;
+    if (a->nbytes && !a->text) return false;
+    if ((a->cap && !a->out) || (a->deferred_cap && (!a->deferred || !a->ndeferred))) return false;
+    if (a->nbytes && a->cap) {                                // out must not overlap text
+        const uintptr_t i0 = (uintptr_t) a->text, i1 = i0 + a->nbytes, o0 = (uintptr_t) a->out, o1 = o0 + a->cap;
+        if (i0 < o1 && o0 < i1) return false;
+    }
+    return true;
+}
+
+static void uat_report(const struct mgpu_uat_args *a, const UatCounts &n) {
+    *a->bytes = n.frames * kUatFrameText;
+    *a->consumed = n.consumed;
+    *a->nlines = n.lines;
+    *a->nframes = n.frames;
+    if (a->nshort) *a->nshort = n.nshort;
+    if (a->ndeferred) *a->ndeferred = n.deferred;
+}
+
+static int uat_verdict(mgpu_ctx *c, const struct mgpu_uat_args *a, const UatCounts &n) {
+    if (n.frames * kUatFrameText > a->cap) { c->err = "uat encode: output buffer too small"; return MGPU_E_OVERFLOW; }
+    if ((a->msgs || a->sig || a->line_of) && n.frames > a->msgs_cap) { c->err = "uat encode: more frames than the per-frame arrays hold"; return MGPU_E_OVERFLOW; }
+    if (n.deferred > a->deferred_cap) { c->err = "uat encode: more deferred lines than the list holds"; return MGPU_E_OVERFLOW; }
+    return MGPU_OK;
+}
+
+int mgpu_uat_encode_device(mgpu_ctx *c, const struct mgpu_uat_args *a) {
+    if (!c || !uat_args_ok(a)) return MGPU_E_INVAL;
+    UatCounts n = {0, 0, 0, 0, 0};
+    uat_report(a, n);
+    if (a->nbytes == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (int rc = uat_encode_dev(c, *a, 0, 0, &n)) return rc;
+    uat_report(a, n);
+    return uat_verdict(c, a, n);
+}
+
+constexpr uint64_t kUatDefaultPass = 64ull << 20;            // bytes the host form stages per pass, pass_bytes == 0
+
+int mgpu_uat_encode(mgpu_ctx *c, const struct mgpu_uat_args *a) {
+    if (!c || !uat_args_ok(a)) return MGPU_E_INVAL;
+    UatCounts all = {0, 0, 0, 0, 0};
+    uat_report(a, all);
+    if (a->nbytes == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    Behind &b = *c->behind;
+    const bool records = a->msgs || a->sig || a->line_of;
+    uint64_t pass = std::min<uint64_t>(a->pass_bytes ? a->pass_bytes : kUatDefaultPass, a->nbytes);
+    for (uint64_t at = 0; at < a->nbytes;) {
+        const uint64_t nb = std::min<uint64_t>(pass, a->nbytes - at);
+        // what this pass may write: what the caller's buffers still hold, and no more than nb bytes of text can give
+        const uint64_t most = uat_max_frames(nb);
+        const uint64_t out_room = a->cap > all.frames * kUatFrameText ? std::min<uint64_t>(a->cap - all.frames * kUatFrameText, most * kUatFrameText) : 0;
+        const uint64_t rec_room = records && a->msgs_cap > all.frames ? std::min<uint64_t>(a->msgs_cap - all.frames, most) : 0;
+        if (int rc = b.d_uat_in.reserve(c, nb + 64)) return rc;
+        if (int rc = b.d_uat_out.reserve(c, out_room + 64)) return rc;
+        struct mgpu_uat_args d = *a;
+        d.text = b.d_uat_in.as<uint8_t>(); d.nbytes = nb;
+        d.out = b.d_uat_out.as<uint8_t>(); d.cap = out_room;
+        d.msgs = nullptr; d.sig = nullptr; d.line_of = nullptr; d.msgs_cap = rec_room;
+        if (a->msgs) { if (int rc = b.d_uat_msgs.reserve(c, (rec_room + 1) * sizeof(mgpu_msg))) return rc; d.msgs = b.d_uat_msgs.as<mgpu_msg>(); }
+        if (a->sig) { if (int rc = b.d_uat_sig.reserve(c, rec_room + 64)) return rc; d.sig = b.d_uat_sig.as<uint8_t>(); }
+        if (a->line_of) { if (int rc = b.d_uat_line_of.reserve(c, (rec_room + 1) * sizeof(uint64_t))) return rc; d.line_of = b.d_uat_line_of.as<uint64_t>(); }
+        HIPCHK(c, hipMemcpyAsync(b.d_uat_in.p, a->text + at, nb, hipMemcpyHostToDevice, c->stream_aux));
+        UatCounts n;
+        if (int rc = uat_encode_dev(c, d, all.lines, std::min<uint64_t>(all.deferred, a->deferred_cap), &n)) return rc;
+        if (n.consumed == 0 && at + nb < a->nbytes) {         // a line longer than the pass: a larger pass
+            pass = pass > a->nbytes / 2 ? a->nbytes : 2 * pass;
+            continue;
+        }
+        // (the pass stored the bytes and records below its rooms only: the copies stay inside the caller's buffers)
+        const uint64_t nout = std::min<uint64_t>(n.frames * kUatFrameText, out_room), nrec = std::min<uint64_t>(n.frames, rec_room);
+        if (nout) HIPCHK(c, hipMemcpy(a->out + all.frames * kUatFrameText, d.out, nout, hipMemcpyDeviceToHost));
+        if (nrec && a->msgs) HIPCHK(c, hipMemcpy(a->msgs + all.frames, d.msgs, nrec * sizeof(mgpu_msg), hipMemcpyDeviceToHost));
+        if (nrec && a->sig) HIPCHK(c, hipMemcpy(a->sig + all.frames, d.sig, nrec, hipMemcpyDeviceToHost));
+        if (nrec && a->line_of) HIPCHK(c, hipMemcpy(a->line_of + all.frames, d.line_of, nrec * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        all.lines += n.lines; all.frames += n.frames; all.deferred += n.deferred; all.nshort += n.nshort;
+        if (n.consumed == 0) break;                           // the rest has no '\n'
+        at += n.consumed;
+        all.consumed = at;
+    }
+    uat_report(a, all);
+    return uat_verdict(c, a, all);
 }
 
 uint32_t mgpu_crc_checksum(const uint8_t *msg, int bits) { return crc_tables().checksum(msg, bits); }

@@ -43,6 +43,9 @@ struct Behind {
     // form's five optional arrays
     DevBuf d_dump_len, d_dump_forward, d_dump_ids, d_dump_pos, d_dump_nic, d_dump_rc;
     DevBuf d_fields;                                         // the host-array forms' field records
+    // UAT input (kernels/uat.inc): per lane of a tile a halfword; per tile five words and three offsets; the five totals; the deferred
+    // lines' indices; the table of signal bytes, uploaded on first use; the host-array form's staged text and its results
+    DevBuf d_uat_meta, d_uat_blocks, d_uat_off, d_uat_total, d_uat_deferred, d_uat_sig_table, d_uat_in, d_uat_out, d_uat_msgs, d_uat_sig, d_uat_line_of;
     DevBuf d_roll_tan;                                       // tables.h build_roll_tangent_table(), uploaded on first use
     // the first-stage tracking gate (kernels/gate.inc): the aircraft table (1 GiB, allocated and zeroed by the first call), its scratch,
     // the host-array forms' verdicts

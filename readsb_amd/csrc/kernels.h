@@ -281,6 +281,33 @@ struct SnipScratch {
 };
 // iq 16-byte aligned, out 2-byte aligned; quiet_run: the reference's counter before the call; write == false: the counts only
 void launch_snip(const uint8_t *iq, uint64_t n, int32_t level, uint64_t quiet_run, const SnipScratch &w, uint8_t *out, uint64_t cap, bool write, hipStream_t s);
+// UAT input (kernels/uat.inc; uat2esnt over dump978 downlink lines, uat_format.h): a workgroup per tile of the text
+constexpr uint32_t kUatTile = 8192;           // bytes of text per workgroup; a line belongs to the tile that holds its first byte
+constexpr uint32_t kUatHalo = 256;            // = kUatDevLineMax: what a line that starts on a tile's last byte may reach into the next
+constexpr uint64_t kUatMaxBytes = (uint64_t) kUatTile * 0x7fffffffull;   // a grid's limit
+struct UatParams {
+    const uint8_t *text;              // any alignment
+    uint64_t nbytes;
+    const uint8_t *sigtab;            // uat_build_sig_table()
+    uint8_t *out;                     // the AVR lines; nothing at or beyond out + cap is stored
+    uint64_t cap;
+    mgpu_msg *msgs;                   // the three optional per-frame arrays, msgs_cap entries each
+    uint8_t *sig;
+    unsigned long long *line_of;
+    uint64_t msgs_cap;
+    unsigned long long *deferred;     // deferred_cap line indices
+    uint64_t deferred_cap;
+    uint64_t line_base;               // added to every line index (the host form's passes)
+    int64_t now_ms;
+};
+struct UatScratch {
+    uint16_t *meta;                   // [stride * kBlock] per lane of a tile: frames of its lines | deferred lines << 8
+    uint32_t *blocks;                 // [5 * stride] per tile: newlines | 1 + the last one's offset (0: none) | frames | deferred lines | short lines
+    unsigned long long *off;          // [3 * stride] the exclusive prefix sums of newlines, frames, deferred lines
+    unsigned long long *total;        // [5] lines, bytes consumed, frames, deferred lines, short lines
+    size_t stride;                    // >= ceil(nbytes / kUatTile)
+};
+void launch_uat_encode(const UatParams &a, const UatScratch &w, hipStream_t s);
 // stable merge of message lists by timestamp (kernels/merge.inc): segs [nseg] in device memory, scratch = merge_scratch_bytes(n, nseg)
 struct MergeSeg {
     const mgpu_msg *msgs;
