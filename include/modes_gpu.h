@@ -302,7 +302,9 @@ uint64_t mgpu_pending_messages(mgpu_ctx *ctx);
 /* icaoFilterExpire() (icao_filter.c:96-110) / icaoFilterAdd() (:112-130) on the context's filter, between two feed
  * calls.  mgpu_filter_expire is how a host drives the filter with cfg.filter_clock = MGPU_FILTER_CLOCK_EXTERNAL (it is
  * refused with MGPU_E_INVAL in the other modes: two clocks would double-flip); mgpu_filter_add mirrors adds the host
- * makes outside the demodulator (decodeModesMessage on network input, mode_s.c:766-779) and is allowed in every mode. */
+ * makes outside the demodulator (decodeModesMessage on network input, mode_s.c:766-779) and is allowed in every mode: an
+ * address added this way is known to the device's pre-screen too, whether or not the stream ever carries it as DF11 / DF17.
+ * Both calls wait for deferred feeds in flight first. */
 int mgpu_filter_expire(mgpu_ctx *ctx);
 int mgpu_filter_add(mgpu_ctx *ctx, uint32_t addr);
 

@@ -232,27 +232,36 @@ static void checksum_fix(uint8_t *msg, const struct einfo *e) {
  * inactive generation, `occupied` (new inserts into the active generation since the last
  * flip/resize) and the table size, because growing (occupied > buckets/3) re-inserts only the
  * ACTIVE generation and silently empties the inactive one (icaoFilterResize, :65-93). */
-struct gen { uint8_t *present; uint32_t *members; uint32_t n, cap; int has_baddr; };
+struct gen { uint8_t *present; uint32_t *members; uint32_t n, cap; uint32_t big[64]; uint32_t nbig; };
 static struct gen g_gen[2];
 static int g_active;
 static uint32_t g_occupied, g_filter_bits;
 
 static void gen_clear(struct gen *g) {
     for (uint32_t i = 0; i < g->n; i++) g->present[g->members[i]] = 0;
-    g->n = 0; g->has_baddr = 0;
+    g->n = 0; g->nbig = 0;
+}
+/* addresses >= 2^24 (Modes.show_only's default, and whatever else a host adds: no frame carries one, but each takes a bucket) */
+static int gen_has_big(const struct gen *g, uint32_t addr) {
+    for (uint32_t i = 0; i < g->nbig; i++) if (g->big[i] == addr) return 1;
+    return 0;
 }
 static int gen_has(const struct gen *g, uint32_t addr) {
-    return addr < (1u << 24) ? g->present[addr] : (addr == BADDR && g->has_baddr);
+    return addr < (1u << 24) ? g->present[addr] : gen_has_big(g, addr);
 }
 static int gen_add(struct gen *g, uint32_t addr) {   /* returns 1 if newly inserted */
     if (gen_has(g, addr)) return 0;
-    if (addr >= (1u << 24)) { g->has_baddr = 1; return 1; }
+    if (addr >= (1u << 24)) {
+        if (g->nbig == sizeof(g->big) / sizeof(g->big[0])) { fprintf(stderr, "modes_oracle: too many addresses >= 2^24\n"); abort(); }
+        g->big[g->nbig++] = addr;
+        return 1;
+    }
     if (g->n == g->cap) { g->cap = g->cap ? g->cap * 2 : 1024; g->members = realloc(g->members, g->cap * sizeof(uint32_t)); }
     g->present[addr] = 1;
     g->members[g->n++] = addr;
     return 1;
 }
-static uint32_t gen_size(const struct gen *g) { return g->n + (g->has_baddr ? 1 : 0); }
+static uint32_t gen_size(const struct gen *g) { return g->n + g->nbig; }
 
 static void filter_init(void) {                       /* icaoFilterInit, :47-59 */
     for (int i = 0; i < 2; i++) {

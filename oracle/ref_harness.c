@@ -87,6 +87,66 @@ void ref_set_mode_ac(int on) { g_mode_ac = on; }
 static int g_flip_before;   /* the reference program's other start-up order: first icaoFilterExpire() before buffer 0 */
 void ref_set_flip_before(int on) { g_flip_before = on; }
 
+/* A filter script (tests/filter_util.py): what a host that keeps its own filter forwards between buffers.  Lines
+ * "<buffers so far> E" = icaoFilterExpire(), "<buffers so far> A <hex>" = icaoFilterAdd(addr); each is applied, in file order, before
+ * the buffer with that index is demodulated (an index of the buffer count or beyond: after the last buffer).  With external = 1
+ * (mgpu_config.filter_clock 2) the harness's own 60 s rule is off and only the script expires.  trace (optional): after every
+ * buffer, the number of messages so far (u64) and the counters so far (struct oracle_stats). */
+struct script_op { uint64_t at; int expire; uint32_t addr; };
+static struct script_op *g_script;
+static size_t g_nscript, g_script_next;
+static int g_external;
+static FILE *g_trace;
+
+int ref_set_filter_script(const char *path, int external, const char *trace_path) {
+    FILE *f = fopen(path, "r");
+    if (!f) { perror(path); return -1; }
+    char line[128];
+    size_t cap = 0;
+    while (fgets(line, sizeof(line), f)) {
+        unsigned long long at; char op; unsigned addr = 0;
+        const int n = sscanf(line, "%llu %c %x", &at, &op, &addr);
+        if (n <= 0) continue;
+        if (!((n == 2 && op == 'E') || (n == 3 && op == 'A')) || (g_nscript && at < g_script[g_nscript - 1].at)) {
+            fprintf(stderr, "ref_harness: bad script line: %s", line);
+            fclose(f);
+            return -1;
+        }
+        if (g_nscript == cap) { cap = cap ? cap * 2 : 64; g_script = realloc(g_script, cap * sizeof(*g_script)); }
+        g_script[g_nscript++] = (struct script_op) {at, op == 'E', addr};
+    }
+    fclose(f);
+    g_external = external;
+    if (trace_path && !(g_trace = fopen(trace_path, "wb"))) { perror(trace_path); return -1; }
+    return 0;
+}
+
+static void script_apply(uint64_t before_buffer, struct oracle_stats *st) {
+    for (; g_script_next < g_nscript && g_script[g_script_next].at <= before_buffer; g_script_next++) {
+        if (g_script[g_script_next].expire) { icaoFilterExpire(); st->nflips++; }
+        else icaoFilterAdd(g_script[g_script_next].addr);
+    }
+}
+
+static void stats_now(struct oracle_stats *st, uint64_t nbuffers) {
+    struct stats *s = &Modes.stats_current;
+    st->demod_preambles = s->demod_preambles;
+    st->demod_rejected_bad = s->demod_rejected_bad;
+    st->demod_rejected_unknown_icao = s->demod_rejected_unknown_icao;
+    for (int i = 0; i < 3; i++) st->demod_accepted[i] = s->demod_accepted[i];
+    for (int i = 0; i < 5; i++) { st->demod_preamblePhase[i] = s->demod_preamblePhase[i]; st->demod_bestPhase[i] = s->demod_bestPhase[i]; }
+    st->strong_signal_count = s->strong_signal_count;
+    st->signal_power_count = s->signal_power_count;
+    st->noise_power_count = s->noise_power_count;
+    st->samples_processed = s->samples_processed;
+    st->samples_lost = s->samples_lost;
+    st->nbuffers = nbuffers;
+    st->signal_power_sum = s->signal_power_sum;
+    st->noise_power_sum = s->noise_power_sum;
+    st->peak_signal_power = s->peak_signal_power;
+    st->demod_modeac = s->demod_modeac;
+}
+
 static struct converter_state *g_cstate;
 static iq_convert_fn g_conv;
 static int g_configured;
@@ -174,6 +234,7 @@ int ref_demod_run(int format, int nfix, int fixdf, int thr,
         uint64_t remain = nsamples - sampleCounter;
         unsigned slen = remain >= B ? B : (unsigned) remain;
         if (slen < B) eof = 1;   /* short (possibly zero-length) read ends the file, sdr_ifile.c:223-237 */
+        script_apply(k, st);
 
         outbuf->sampleTimestamp = sampleCounter * 12e6 / Modes.sample_rate;
         if (k > 0 && lastbuf->length >= TR)
@@ -202,29 +263,21 @@ int ref_demod_run(int format, int nfix, int fixdf, int thr,
         Modes.stats_current.samples_lost += B - outbuf->length;
 
         int64_t now = Modes.synthetic_now;      /* mstime() for ifile input, util.c:58-60 */
-        if (now >= next_flip) {                 /* readsb.c:1227-1231 */
+        if (!g_external && now >= next_flip) {  /* readsb.c:1227-1231 */
             icaoFilterExpire();
             next_flip = now + MODES_ICAO_FILTER_TTL;
             st->nflips++;
         }
         k++;
+        if (g_trace) {
+            stats_now(st, k);
+            fwrite(&g_nout, sizeof(g_nout), 1, g_trace);
+            fwrite(st, sizeof(*st), 1, g_trace);
+        }
     }
-    struct stats *s = &Modes.stats_current;
-    st->demod_preambles = s->demod_preambles;
-    st->demod_rejected_bad = s->demod_rejected_bad;
-    st->demod_rejected_unknown_icao = s->demod_rejected_unknown_icao;
-    for (int i = 0; i < 3; i++) st->demod_accepted[i] = s->demod_accepted[i];
-    for (int i = 0; i < 5; i++) { st->demod_preamblePhase[i] = s->demod_preamblePhase[i]; st->demod_bestPhase[i] = s->demod_bestPhase[i]; }
-    st->strong_signal_count = s->strong_signal_count;
-    st->signal_power_count = s->signal_power_count;
-    st->noise_power_count = s->noise_power_count;
-    st->samples_processed = s->samples_processed;
-    st->samples_lost = s->samples_lost;
-    st->nbuffers = k;
-    st->signal_power_sum = s->signal_power_sum;
-    st->noise_power_sum = s->noise_power_sum;
-    st->peak_signal_power = s->peak_signal_power;
-    st->demod_modeac = s->demod_modeac;
+    script_apply(UINT64_MAX, st);
+    if (g_trace) { fclose(g_trace); g_trace = NULL; }
+    stats_now(st, k);
     *out = g_out; *nout = g_nout;
     for (int i = 0; i < 2; i++) free(bufs[i].data);
     return 0;
@@ -364,8 +417,14 @@ static void *read_file(const char *path, uint64_t *size) {
 
 /* ref_demod <UC8|SC16|SC16Q11> <nfix> <fixdf> <thr> <in.iq> <out.msgs> [out.stats] [out.mag]
  * out.msgs : array of struct oracle_msg;  out.stats : one struct oracle_stats;
- * out.mag  : u16 delayed magnitude stream (326 zeros + one magnitude per sample) */
+ * out.mag  : u16 delayed magnitude stream (326 zeros + one magnitude per sample)
+ * ref_demod --capabilities : what this build takes beyond that, one word per line (tests/helpers.py asks before it relies on one:
+ * a build from an earlier harness ignores the variables it does not know and answers this with its usage line) */
 int main(int argc, char **argv) {
+    if (argc == 2 && !strcmp(argv[1], "--capabilities")) {
+        puts("filter-script");
+        return 0;
+    }
     if (argc < 7) {
         fprintf(stderr, "usage: %s <UC8|SC16|SC16Q11> <nfix> <fixdf> <thr> <in.iq> <out.msgs> [out.stats] [out.mag]\n", argv[0]);
         return 2;
@@ -379,6 +438,15 @@ int main(int argc, char **argv) {
     uint16_t *mag = argc > 8 ? malloc((n + 326) * sizeof(uint16_t)) : NULL;
     if (getenv("ORACLE_MODE_AC")) ref_set_mode_ac(1);
     if (getenv("ORACLE_FLIP_BEFORE")) ref_set_flip_before(1);
+    /* ORACLE_FILTER_SCRIPT=<file>: the filter script; its trace goes to <file>.trace.  ORACLE_FILTER_EXTERNAL: clock mode 2 */
+    if (getenv("ORACLE_FILTER_SCRIPT")) {
+        char trace[4096];
+        snprintf(trace, sizeof(trace), "%s.trace", getenv("ORACLE_FILTER_SCRIPT"));
+        if (ref_set_filter_script(getenv("ORACLE_FILTER_SCRIPT"), getenv("ORACLE_FILTER_EXTERNAL") != NULL, trace) < 0) return 2;
+    } else if (getenv("ORACLE_FILTER_EXTERNAL")) {
+        fprintf(stderr, "ref_demod: ORACLE_FILTER_EXTERNAL needs ORACLE_FILTER_SCRIPT\n");
+        return 2;
+    }
     if (ref_demod_run(format, nfix, fixdf, thr, iq, n, &out, &nout, &st, mag, NULL, NULL) < 0)
         return 1;
     FILE *f = fopen(argv[6], "wb");

@@ -1922,6 +1922,18 @@ int mgpu_filter_add(mgpu_ctx *c, uint32_t addr) {
     if (!c) return MGPU_E_INVAL;
     { const int rc = drain(c); if (rc != MGPU_OK) return rc; }
     c->resolver.filter().add(addr);
+    // The pre-screen drops every conditional record whose address has no bit in the adder bitmap before the walk asks the filter, and
+    // no frame of this stream may ever set this one (the host learnt the address elsewhere).  Nothing is in flight behind the drain:
+    // a plain read-modify-write of the one word.  (An address >= 2^24 matches no frame and has no bit.)
+    if (addr < (1u << 24)) {
+        HIPCHK(c, hipSetDevice(c->cfg.device));
+        uint32_t word = 0;
+        HIPCHK(c, hipMemcpy(&word, c->d_adder_bitmap + (addr >> 5), sizeof(word), hipMemcpyDeviceToHost));
+        if (!(word & (1u << (addr & 31)))) {
+            word |= 1u << (addr & 31);
+            HIPCHK(c, hipMemcpy(c->d_adder_bitmap + (addr >> 5), &word, sizeof(word), hipMemcpyHostToDevice));
+        }
+    }
     return MGPU_OK;
 }
 

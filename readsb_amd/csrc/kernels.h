@@ -107,7 +107,7 @@ struct SweepParams {
     uint32_t *cand_count;     // [steps], + one empty list behind an odd number of steps
     uint32_t pace_recip;      // k_sweep: 2^32 / reference step time in 10 ns ticks (set by launch_sweep; 0 = no pacing)
     uint32_t *sweep_part;     // [k_slice workgroups][8] partial counters (records, candidates, phases 4/5, 6/7, 8), summed by the pre-screen write pass
-    uint32_t *adder_bitmap;   // 2^24 bits: addresses some clean DF17 / DF11 IID 0 frame carries
+    uint32_t *adder_bitmap;   // 2^24 bits: addresses some clean DF17 / DF11 IID 0 frame carries, and those the host added (mgpu_filter_add)
     unsigned long long *counters;   // [CNT_NUM]
     // k_sweep_uc8 (converter and sweep in one; iq == nullptr: k_sweep over the magnitudes in `mag`): the chunk's UC8 samples, the 326
     // magnitudes before the chunk (nullptr: zeros), the 128 x 128 symmetric table (tables.h: UC8_SYM_OFFSET), where the magnitudes

@@ -2,9 +2,11 @@
 // Part of the single translation unit kernels.hip (included inside namespace mgpu, after the parts before it).
 
 // =============================================================================================
-// pre-screen: a conditional record (score_unknown < 0) can only matter if its address is one
-// that some clean DF17 / DF11-IID0 frame of this stream carries (the only frames that ever add
-// to the ICAO filter, mode_s.c:766-779).  Everything else is "rejected_unknown_icao" for sure.
+// pre-screen: a conditional record (score_unknown < 0) can only matter if its address has a bit in
+// the adder bitmap: one that some clean DF17 / DF11-IID0 frame of this stream carries (the only
+// frames that add to the ICAO filter, mode_s.c:766-779; k_slice sets their bits), or one the host
+// added from outside (mgpu_filter_add sets its bit: network input the demodulator never sees).
+// Everything else is "rejected_unknown_icao" for sure.
 // The COUNT pass decides which records live and leaves the decision as a 64-bit mask in each segment header (a segment = the
 // records one scoring pass of k_slice wrote for one tile: at most 64); the WRITE pass compacts the live records in stream order.
 // It reads the masks, not the adder bitmap: it may run beside the next chunk's sweep, which adds bits to the bitmap (a second

@@ -84,6 +84,11 @@ def oracle_lib():
         lib.modes_oracle_crc_init.argtypes = [C.c_int]
         lib.modes_oracle_diagnose.argtypes = [C.c_uint32, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.modes_oracle_table_size.argtypes = [C.c_int]
+        lib.modes_oracle_stream_begin.argtypes = [C.POINTER(OracleCfg), C.c_int64]
+        lib.modes_oracle_stream_mag_buf.argtypes = [C.c_void_p, C.c_uint32, C.c_int64, C.c_int64, C.c_double, C.c_double]
+        lib.modes_oracle_stream_take.argtypes = [C.POINTER(C.c_void_p), C.c_void_p]
+        lib.modes_oracle_stream_take.restype = C.c_uint64
+        lib.modes_oracle_stream_filter_add.argtypes = [C.c_uint32]
         _oracle = lib
     return _oracle
 
@@ -109,12 +114,96 @@ def oracle_run(iq, fmt=0, nfix=1, fixdf=1, thr=58, want_mag=False, mode_ac=0, fi
     return (msgs, st[0], mag) if want_mag else (msgs, st[0])
 
 
-def reference_run(iq, fmt=0, nfix=1, fixdf=1, thr=58, want_mag=False, mode_ac=0, flip_before=False):
+BUF_SAMPLES, TRAILING = 131072, 326
+SHOW_ONLY = 0xff123456       # modesInit's icaoFilterAdd(Modes.show_only) (readsb.c:310): the filter's first entry
+
+
+def _script_grid(ops, fmt):
+    """-> [(first buffer, buffers)] per feed, [(buffers so far, op)] for the other operations, the concatenated IQ bytes."""
+    grid, others, nbuf, parts, short = [], [], 0, [], False
+    for op in ops:
+        if op[0] == "feed":
+            iq = np.ascontiguousarray(op[1]).view(np.uint8).reshape(-1)
+            n = iq.size // FMT_BYTES[fmt]
+            assert n > 0 and not short, "only the last feed of a script may end short"
+            short = n % BUF_SAMPLES != 0
+            nb = -(-n // BUF_SAMPLES)
+            grid.append((nbuf, nb))
+            nbuf += nb
+            parts.append(iq)
+        else:
+            assert op[0] in ("expire", "add")
+            others.append((nbuf, op))
+    assert short, "a script's last feed ends short (an exact multiple has the reader push one more, empty, buffer)"
+    return grid, others, np.concatenate(parts)
+
+
+def oracle_stream(ops, fmt=0, nfix=1, fixdf=1, thr=58, mode_ac=0, filter_clock=0):
+    """Our CPU restatement driven by a filter script (what a host that keeps its own ICAO filter forwards between feeds):
+    ops = [("feed", iq) | ("expire",) | ("add", addr)] in stream order, filter_clock = mgpu_config.filter_clock.  The buffer grid is
+    ifileRun's, walked as tests/host_stub/modes_gpu_standin.c walks it.  With filter_clock 2 the library starts empty and the script
+    itself starts with ("add", SHOW_ONLY), as modesInit does; modes_oracle_stream_begin has made that add already.
+    -> [(messages, counters)] per feed, the counters as they stand right after the feed."""
+    lib = oracle_lib()
+    _script_grid(ops, fmt)
+    ops = list(ops)
+    if filter_clock == 2:
+        assert ops and tuple(ops[0]) == ("add", SHOW_ONLY), "a filter_clock 2 script starts with modesInit's add of show_only"
+        ops = ops[1:]
+    lib.modes_oracle_set_mode_ac(int(mode_ac))
+    lib.modes_oracle_set_filter_clock(int(filter_clock))
+    cfg = OracleCfg(fmt, nfix, fixdf, thr)
+    lib.modes_oracle_stream_begin(C.byref(cfg), STARTUP_MS)
+    bufs = [np.zeros(BUF_SAMPLES + TRAILING, dtype=np.uint16) for _ in range(2)]
+    lens, k, counter, out = [0, 0], 0, 0, []
+    try:
+        for op in ops:
+            if op[0] == "expire":
+                lib.modes_oracle_stream_filter_expire()
+            elif op[0] == "add":
+                lib.modes_oracle_stream_filter_add(int(op[1]))
+            else:
+                iq = np.ascontiguousarray(op[1]).view(np.uint8).reshape(-1)
+                n = iq.size // FMT_BYTES[fmt]
+                for off in range(0, n, BUF_SAMPLES):
+                    slen = min(BUF_SAMPLES, n - off)
+                    cur, last, lastlen = bufs[k & 1], bufs[(k + 1) & 1], lens[(k + 1) & 1]
+                    cur[:TRAILING] = last[lastlen:lastlen + TRAILING] if k > 0 and lastlen >= TRAILING else 0
+                    piece = iq[off * FMT_BYTES[fmt]:(off + slen) * FMT_BYTES[fmt]]
+                    ml, mp = C.c_double(), C.c_double()
+                    lib.modes_oracle_convert(fmt, piece.ctypes.data, cur[TRAILING:].ctypes.data, slen, C.byref(ml), C.byref(mp))
+                    lens[k & 1] = slen
+                    st = counter * 5
+                    lib.modes_oracle_stream_mag_buf(cur.ctypes.data, slen, st, st // 12000 + STARTUP_MS, ml.value, mp.value)
+                    counter += slen
+                    k += 1
+                ptr, stats = C.c_void_p(), np.zeros(1, dtype=ORACLE_STATS)
+                nout = lib.modes_oracle_stream_take(C.byref(ptr), stats.ctypes.data)
+                msgs = np.zeros(nout, dtype=ORACLE_MSG)
+                if nout:
+                    C.memmove(msgs.ctypes.data, ptr.value, nout * ORACLE_MSG.itemsize)
+                lib.modes_oracle_free(ptr)
+                out.append((msgs, stats[0]))
+    finally:
+        lib.modes_oracle_set_mode_ac(0)
+        lib.modes_oracle_set_filter_clock(0)
+    return out
+
+
+def reference_run(iq, fmt=0, nfix=1, fixdf=1, thr=58, want_mag=False, mode_ac=0, flip_before=False, ops=None, filter_clock=None):
     """The checker of the -m gpu parity tests: the reference's OWN objects (oracle/_ref, compiled from the reference's C files in
     place; the prebuilt files travel to the GPU box) where they are there, the restatement otherwise, so that a developer without
     them can still run the suite (tests/test_oracle.py pins the restatement to _ref either way).  That the objects ARE there on a
     GPU run is a test of its own (test_gpu_parity.py::test_reference_objects_are_present), so the fallback cannot pass unnoticed.
-    flip_before = the reference program's other start-up order (oracle_run's filter_clock=1; pinned in tests/test_oracle.py)."""
+    flip_before = the reference program's other start-up order (oracle_run's filter_clock=1; pinned in tests/test_oracle.py).
+    ops = a filter script (oracle_stream) in place of iq, with filter_clock 0 / 1 / 2: -> [(messages, counters)] per feed
+    (the reference's objects where they take scripts, ref_takes_scripts(); tests/test_oracle_filter_script.py pins the restatement
+    to them there)."""
+    if ops is not None:
+        clock = (1 if flip_before else 0) if filter_clock is None else filter_clock
+        if ref_takes_scripts():
+            return ref_run(None, fmt, nfix, fixdf, thr, mode_ac=mode_ac, ops=ops, filter_clock=clock)
+        return oracle_stream(ops, fmt, nfix, fixdf, thr, mode_ac=mode_ac, filter_clock=clock)
     if have_ref():
         return ref_run(iq, fmt, nfix, fixdf, thr, want_mag=want_mag, mode_ac=mode_ac, flip_before=flip_before)
     return oracle_run(iq, fmt, nfix, fixdf, thr, want_mag=want_mag, mode_ac=mode_ac, filter_clock=1 if flip_before else 0)
@@ -134,11 +223,38 @@ def have_ref():
     return os.path.exists(REF_BIN)
 
 
-def ref_run(iq, fmt=0, nfix=1, fixdf=1, thr=58, want_mag=False, mode_ac=0, flip_before=False):
-    """The reference's own objects (oracle/_ref/ref_demod), one process per run."""
+_ref_scripts = None
+
+
+def ref_takes_scripts():
+    """Is there a ref_demod, and was it built from a harness that takes filter scripts?  A build from an earlier oracle/ref_harness.c
+    (oracle/_ref is built where the reference tree is, and carried from there) ignores ORACLE_FILTER_SCRIPT without a word, so the
+    program is asked (`ref_demod --capabilities`).  Without one, scripts go to the restatement, exactly as every run does where
+    oracle/_ref is missing; the per-feed counts of tests/filter_util.py's RECORDED, taken from _ref, hold either way."""
+    global _ref_scripts
+    if _ref_scripts is None:
+        _ref_scripts = False
+        if have_ref():
+            r = subprocess.run([REF_BIN, "--capabilities"], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
+            _ref_scripts = r.returncode == 0 and "filter-script" in r.stdout.split()
+    return _ref_scripts
+
+
+REF_TRACE = np.dtype([("nout", "<u8"), ("stats", ORACLE_STATS)])      # ref_harness.c's trace: one record after every buffer
+
+
+def ref_run(iq, fmt=0, nfix=1, fixdf=1, thr=58, want_mag=False, mode_ac=0, flip_before=False, ops=None, filter_clock=None):
+    """The reference's own objects (oracle/_ref/ref_demod), one process per run.  ops = a filter script (oracle_stream) in place
+    of iq, filter_clock 0 / 1 / 2 with it: -> [(messages, counters)] per feed."""
+    grid = None
+    if ops is not None:
+        assert iq is None and not want_mag
+        assert ref_takes_scripts(), f"{REF_BIN} is missing or was built from a harness without filter scripts: `make -C oracle ref`"
+        grid, others, iq = _script_grid(ops, fmt)
+        flip_before = filter_clock == 1
     iq = np.ascontiguousarray(iq).view(np.uint8).reshape(-1)
     with tempfile.TemporaryDirectory() as d:
-        fin, fm, fs, fg = (os.path.join(d, x) for x in ("in.iq", "out.msgs", "out.stats", "out.mag"))
+        fin, fm, fs, fg, fscript = (os.path.join(d, x) for x in ("in.iq", "out.msgs", "out.stats", "out.mag", "script.txt"))
         iq.tofile(fin)
         cmd = [REF_BIN, FMT_NAMES[fmt], str(nfix), str(fixdf), str(thr), fin, fm, fs] + ([fg] if want_mag else [])
         env = dict(os.environ)
@@ -146,12 +262,28 @@ def ref_run(iq, fmt=0, nfix=1, fixdf=1, thr=58, want_mag=False, mode_ac=0, flip_
             env["ORACLE_MODE_AC"] = "1"
         else:
             env.pop("ORACLE_MODE_AC", None)
-        env.pop("ORACLE_FLIP_BEFORE", None)
+        for name in ("ORACLE_FLIP_BEFORE", "ORACLE_FILTER_SCRIPT", "ORACLE_FILTER_EXTERNAL"):
+            env.pop(name, None)
         if flip_before:
             env["ORACLE_FLIP_BEFORE"] = "1"
+        if grid is not None:
+            with open(fscript, "w") as f:
+                for nbuf, op in others:
+                    f.write(f"{nbuf} E\n" if op[0] == "expire" else f"{nbuf} A {int(op[1]):x}\n")
+            env["ORACLE_FILTER_SCRIPT"] = fscript
+            if filter_clock == 2:
+                env["ORACLE_FILTER_EXTERNAL"] = "1"
         subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL, env=env)
         msgs = np.fromfile(fm, dtype=ORACLE_MSG)
         st = np.fromfile(fs, dtype=ORACLE_STATS)[0]
+        if grid is not None:
+            trace = np.fromfile(fscript + ".trace", dtype=REF_TRACE)
+            assert len(trace) == grid[-1][0] + grid[-1][1] and (len(trace) == 0 or trace["nout"][-1] == len(msgs))
+            out = []
+            for first, nb in grid:
+                lo = int(trace["nout"][first - 1]) if first else 0
+                out.append((msgs[lo:int(trace["nout"][first + nb - 1])], trace["stats"][first + nb - 1]))
+            return out
         if want_mag:
             return msgs, st, np.fromfile(fg, dtype=np.uint16)
     return msgs, st
