@@ -1162,6 +1162,105 @@ int mgpu_debug_device_walk(mgpu_ctx *ctx, uint64_t out[8]);
  * reads magnitudes back. */
 int mgpu_debug_last_magnitudes(mgpu_ctx *ctx, uint16_t *out, uint64_t n);
 
+/* ---- SBS input: BaseStation lines to aircraft records (`--net-sbs-in-port`, the MLAT results port, the JAERO and PRIO ports;
+ *      decodeSbsLine, net_io.c:2952-3178, behind readAscii, net_io.c:4599-4641) ------------------------------------------------------
+ *
+ * text is a byte stream.  Framing as readAscii's (:4607-4631): a line ends at '\n' or at a NUL byte (the reference turns every NUL
+ * into '\n' first); bytes behind the last terminator are not consumed: *consumed says how many were, and the caller carries the rest
+ * into its next call, as readsb's client buffer does.  One trailing '\r' of a line of two bytes or more is removed before the length
+ * is taken (:4627).  Length below 2: a heartbeat, no record, counted nowhere (:2958).  Length below 20 or at least 200: invalid
+ * (:2960), counted in *ninvalid.  No line needs more than 201 bytes looked at, so none is deferred for its length.
+ *   One record per valid line, in line order, to recs; line_of (optional) gets the index of its source line, counted from the start
+ *   of this call's text over every terminated line.  A record holds every member decodeSbsLine leaves in a memset-0 modesMessage,
+ *   under the reference's names (struct mgpu_sbs_rec below).
+ *   Fields (t[1] .. t[22] of :3002-3006): fewer than 21 commas is invalid; everything behind the 22nd comma is ignored.  t[1] must be
+ *     "MSG" (:3009).  t[2] has length 1 (:3012); sbsMsgType is its digit, 0 for any other character (atoi, :3015).  t[5] is six hex
+ *     digits of either case (:3017-3030).  Callsign (:3035-3051): strncpy of 9 bytes with byte 8 cleared; NULs up to the first bad
+ *     character (not A-Z, 0-9, ' ') become spaces and the loop breaks there, so the bytes behind it stay as copied; all 8 bytes are in
+ *     the record whether MGPU_F_CALLSIGN_VALID or not.  baro_alt (:3053-3060) is stored even where the range test (-5000, 100000)
+ *     leaves MGPU_F_BARO_ALT_VALID clear.  MGPU_F_GS_VALID iff the float gs_v0 > 0 (:3062-3067).  heading with HEADING_GROUND_TRACK
+ *     (:3069-3074).  decoded_lat / decoded_lon only where both tokens are non-empty, MGPU_SBS_POS_VALID iff both values != 0
+ *     (:3076-3082).  baro_rate (:3084-3088).  The squawk only if strtol > 0, squawkHex = squawkDec2Hex (:3090-3098, track.h:742).
+ *     t[19] (:3100-3111): receiverCountMlat if > 0 and source == SOURCE_MLAT, otherwise "0" / "-1" set the alert.  t[20] (:3114-3129):
+ *     mlatEPU, clamped to 65535, if > 0 and SOURCE_MLAT; otherwise the emergency flag, decided by comparing t[21] — not t[20] — with
+ *     "0" / "-1" (:3122-3127), exactly as written.  t[21] (:3132-3140): SPI from "1" / "0" only; the "-1" the reference's own writer
+ *     prints is not recognised.  t[22] (:3143-3150): matched by prefix, "-1" (AG_GROUND) then "0" (AG_AIRBORNE).
+ *   Numbers, exact: the device takes a numeric token in plain form only.  atoi / strtol tokens (t[12], t[17] - t[20]):
+ *     [+-]?[0-9]{1,9} up to the token's end.  strtod tokens (t[13] - t[16]): [+-]?[0-9]*(\.[0-9]*)? with at least one digit, at most
+ *     15 significant digits behind the leading zeros and at most 22 digits behind the point: the value is M / 10^f with M < 2^53 and
+ *     10^f exact, one IEEE double division, which is what glibc's strtod returns; gs_v0 and heading are that double converted to
+ *     float, as the reference's assignment does.  A line that would be valid but holds a numeric token the reference parses in any
+ *     other form (exponent, blanks, inf, hex, trailing garbage, no digit, too many digits) is DEFERRED: it gets no record, its index
+ *     is listed in `deferred` (ascending; *ndeferred of them), and mgpu_sbs_parse_host gives its record with the host's libc; that
+ *     record belongs in front of the first record whose line_of is larger.
+ *   Not modelled: Modes.receiver_focus (:2956); the debug_garbage log (:3170-3175); the statistics counters
+ *     remote_received_basestation_valid / _invalid, which *nrecs (+ the deferred lines) and *ninvalid give.
+ *   args->size smaller than sizeof(struct mgpu_sbs_in_args), a NULL ctx, args, consumed, nlines or nrecs, text NULL with nbytes != 0,
+ *     recs NULL with recs_cap != 0, deferred or ndeferred NULL with deferred_cap != 0, a source other than SOURCE_SBS (3), SOURCE_MLAT
+ *     (4), SOURCE_JAERO (6), SOURCE_PRIO (11) — what `remote - 64` selects, :2970-2991 —: MGPU_E_INVAL.  nbytes == 0: MGPU_OK with
+ *     zeros.  More records than recs_cap or more deferred lines than deferred_cap: MGPU_E_OVERFLOW with *nrecs and *ndeferred = what
+ *     is needed; nothing is stored at or beyond any capacity.
+ *   mgpu_sbs_decode: every array in host memory; the text goes through the library's device scratch in passes of pass_bytes bytes
+ *     (0: the library's default) cut at line ends, so it may be larger than the device's memory.
+ *   mgpu_sbs_decode_device: text, recs, line_of device pointers (text at any alignment, recs and line_of 8-byte aligned); the
+ *     counters and the deferred list are in host memory in both forms.  nbytes < 2^31 * 8192.  pass_bytes is ignored. */
+#define MGPU_SBS_POS_VALID        (1u << 0)   /* sbs_pos_valid */
+#define MGPU_SBS_EMERGENCY_VALID  (1u << 1)   /* squawk_emergency_valid */
+#define MGPU_SBS_EMERGENCY        (1u << 2)   /* squawk_emergency */
+#define MGPU_SBS_SOURCE_SBS   3u              /* datasource_t, readsb.h:159-173 */
+#define MGPU_SBS_SOURCE_MLAT  4u
+#define MGPU_SBS_SOURCE_JAERO 6u
+#define MGPU_SBS_SOURCE_PRIO  11u
+/* 96 bytes = six 16-byte vectors; no implicit padding, and the reserved members are ZERO: records are compared bytewise. */
+struct mgpu_sbs_rec {
+    int64_t sysTimestamp;              /* now_ms (:3160) */
+    double decoded_lat, decoded_lon;
+    uint32_t addr;
+    uint32_t flags;                    /* MGPU_F_BARO_ALT_VALID, _GS_VALID, _HEADING_VALID, _BARO_RATE_VALID, _SQUAWK_VALID, _CALLSIGN_VALID,
+                                        * _SPI_VALID, _SPI, _ALERT_VALID, _ALERT */
+    uint32_t sbs_flags;                /* MGPU_SBS_* */
+    int32_t baro_alt, baro_rate;
+    float gs_v0, heading;
+    uint32_t squawkDec, squawkHex;
+    int32_t receiverCountMlat, mlatEPU;
+    char callsign[8];
+    uint8_t sbsMsgType, source, addrtype, airground;
+    uint8_t baro_alt_unit, heading_type;
+    uint8_t reserved[14];              /* 0 */
+};
+#ifdef __cplusplus
+static_assert(sizeof(struct mgpu_sbs_rec) == 96, "struct mgpu_sbs_rec");
+#else
+_Static_assert(sizeof(struct mgpu_sbs_rec) == 96, "struct mgpu_sbs_rec");
+#endif
+struct mgpu_sbs_in_args {
+    uint32_t size;                     /* sizeof(struct mgpu_sbs_in_args) */
+    uint32_t source;                   /* MGPU_SBS_SOURCE_* */
+    const uint8_t *text;
+    uint64_t nbytes;
+    int64_t now_ms;                    /* the records' sysTimestamp */
+    struct mgpu_sbs_rec *recs;         /* recs_cap entries: one record per valid line */
+    uint64_t *line_of;                 /* optional, recs_cap entries: the source line per record */
+    uint64_t recs_cap;
+    uint64_t *deferred;                /* host, deferred_cap entries: the indices of the deferred lines */
+    uint64_t deferred_cap;
+    uint64_t *consumed;                /* host, out: bytes of text up to and including the last terminator */
+    uint64_t *nlines;                  /* host, out: lines in them */
+    uint64_t *nrecs;                   /* host, out */
+    uint64_t *ninvalid;                /* host, out, optional */
+    uint64_t *ndeferred;               /* host, out, optional (required with deferred_cap != 0) */
+    uint64_t pass_bytes;               /* host form: bytes staged per pass; 0 = the library's default */
+};
+int mgpu_sbs_decode(mgpu_ctx *ctx, const struct mgpu_sbs_in_args *args);
+int mgpu_sbs_decode_device(mgpu_ctx *ctx, const struct mgpu_sbs_in_args *args);
+/* Line `line_index` of a HOST-memory text (args->text, args->nbytes, args->source, args->now_ms; nothing else of args is read),
+ * parsed on the host with every number resolved by the host's strtol and strtod.  Returns 1 with *rec filled, 0 for a line that gives
+ * no record (a heartbeat, an invalid line; *rec is zeroed), or MGPU_E_INVAL (args, rec, a line that does not exist).  Needs no
+ * context and no GPU. */
+int mgpu_sbs_parse_host(const struct mgpu_sbs_in_args *args, uint64_t line_index, struct mgpu_sbs_rec *rec);
+/* The same for a line given by its bytes (without the terminator; a trailing '\r' still on it). */
+int mgpu_sbs_parse_line_host(const uint8_t *line, uint64_t len, uint32_t source, int64_t now_ms, struct mgpu_sbs_rec *rec);
+
 #ifdef __cplusplus
 }
 #endif

@@ -213,6 +213,23 @@ class UatArgs(C.Structure):                                           # struct m
 UAT_FRAME_TEXT = 45                         # bytes of one AVR line of mgpu_uat_encode
 
 
+class SbsInArgs(C.Structure):                                         # struct mgpu_sbs_in_args
+    _fields_ = [("size", C.c_uint32), ("source", C.c_uint32), ("text", C.c_void_p), ("nbytes", C.c_uint64), ("now_ms", C.c_int64), ("recs", C.c_void_p),
+                ("line_of", C.c_void_p), ("recs_cap", C.c_uint64), ("deferred", C.c_void_p), ("deferred_cap", C.c_uint64), ("consumed", C.POINTER(C.c_uint64)),
+                ("nlines", C.POINTER(C.c_uint64)), ("nrecs", C.POINTER(C.c_uint64)), ("ninvalid", C.POINTER(C.c_uint64)), ("ndeferred", C.POINTER(C.c_uint64)),
+                ("pass_bytes", C.c_uint64)]
+
+
+SBS_REC_DTYPE = np.dtype([                                            # struct mgpu_sbs_rec: 96 bytes, reserved = 0
+    ("sysTimestamp", "<i8"), ("decoded_lat", "<f8"), ("decoded_lon", "<f8"), ("addr", "<u4"), ("flags", "<u4"), ("sbs_flags", "<u4"), ("baro_alt", "<i4"),
+    ("baro_rate", "<i4"), ("gs_v0", "<f4"), ("heading", "<f4"), ("squawkDec", "<u4"), ("squawkHex", "<u4"), ("receiverCountMlat", "<i4"), ("mlatEPU", "<i4"),
+    ("callsign", "S8"), ("sbsMsgType", "u1"), ("source", "u1"), ("addrtype", "u1"), ("airground", "u1"), ("baro_alt_unit", "u1"), ("heading_type", "u1"),
+    ("reserved", "u1", 14)])
+assert SBS_REC_DTYPE.itemsize == 96
+SBS_SOURCES = {"sbs": 3, "mlat": 4, "jaero": 6, "prio": 11}          # MGPU_SBS_SOURCE_*: the reference's datasource_t
+SBS_POS_VALID, SBS_EMERGENCY_VALID, SBS_EMERGENCY = 1, 2, 4           # MGPU_SBS_*
+
+
 ABI_VERSION = 6                             # MGPU_ABI_VERSION of the include/modes_gpu.h these ctypes mirrors were written against
 
 
@@ -402,6 +419,10 @@ def load_library():
     lib.mgpu_uat_format_host.restype = C.c_int64
     lib.mgpu_uat_format_line_host.argtypes = [vp, u64, C.c_int64, vp, u64, vp, vp]
     lib.mgpu_uat_format_line_host.restype = C.c_int64
+    lib.mgpu_sbs_decode.argtypes = [vp, C.POINTER(SbsInArgs)]
+    lib.mgpu_sbs_decode_device.argtypes = [vp, C.POINTER(SbsInArgs)]
+    lib.mgpu_sbs_parse_host.argtypes = [C.POINTER(SbsInArgs), u64, vp]
+    lib.mgpu_sbs_parse_line_host.argtypes = [vp, u64, C.c_uint32, C.c_int64, vp]
     lib.mgpu_snip.argtypes = [vp, C.POINTER(SnipArgs)]
     lib.mgpu_snip_device.argtypes = [vp, C.POINTER(SnipArgs)]
     lib.mgpu_merge_by_time.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
@@ -1017,6 +1038,35 @@ class Demodulator:
                 recs.append(rec_buf[:k].copy()); sigs.append(np.full(k, sig_buf.value, dtype=np.uint8)); lines.append(np.full(k, index, dtype=np.uint64))
             take(nframes)
             res.update(text=b"".join(parts), msgs=np.concatenate(recs), sig=np.concatenate(sigs), line_of=np.concatenate(lines))
+        return res
+
+    def sbs_decode(self, text, source="sbs", now_ms=0, settle=True, pass_bytes=0):
+        """mgpu_sbs_decode on a host byte string of BaseStation lines (`--net-sbs-in-port`, the MLAT, JAERO and PRIO ports): one record
+        per valid line, the reference's decodeSbsLine member for member.  source: "sbs", "mlat", "jaero", "prio" or the reference's
+        number.  settle: the lines the device defers (a number outside the plain forms) are parsed on the host (mgpu_sbs_parse_host)
+        and their records put where they belong; otherwise they are left out and listed.
+        -> dict(recs, line_of, consumed, nlines, ninvalid, deferred)."""
+        buf = np.frombuffer(bytes(text), dtype=np.uint8)
+        most = buf.size // 21 + 1                           # a record needs 20 bytes and a terminator (sbs_in_format.h)
+        recs, line_of, deferred = np.zeros(most, dtype=SBS_REC_DTYPE), np.empty(most, dtype=np.uint64), np.empty(most, dtype=np.uint64)
+        c = [C.c_uint64(0) for _ in range(5)]
+        a = SbsInArgs(C.sizeof(SbsInArgs), SBS_SOURCES.get(source, source), buf.ctypes.data if buf.size else None, buf.size, int(now_ms), recs.ctypes.data,
+                      line_of.ctypes.data, most, deferred.ctypes.data, most, *[C.pointer(x) for x in c], int(pass_bytes))
+        self._chk(self.lib.mgpu_sbs_decode(self.ctx, C.byref(a)), "mgpu_sbs_decode")
+        consumed, nlines, nrecs, ninvalid, ndef = (int(x.value) for x in c)
+        res = dict(recs=recs[:nrecs].copy(), line_of=line_of[:nrecs].copy(), consumed=consumed, nlines=nlines, ninvalid=ninvalid, deferred=deferred[:ndef].copy())
+        if settle and ndef:
+            one = np.zeros(1, dtype=SBS_REC_DTYPE)
+            extra_recs, extra_lines = [], []
+            for index in res["deferred"].tolist():
+                rc = int(self.lib.mgpu_sbs_parse_host(C.byref(a), index, one.ctypes.data))
+                if rc < 0:
+                    raise MgpuError(f"mgpu_sbs_parse_host failed ({rc})")
+                if rc:
+                    extra_recs.append(one.copy()); extra_lines.append(index)
+            if extra_lines:
+                where = np.searchsorted(res["line_of"], np.array(extra_lines, dtype=np.uint64))
+                res.update(recs=np.insert(res["recs"], where, np.concatenate(extra_recs)), line_of=np.insert(res["line_of"], where, np.array(extra_lines, dtype=np.uint64)))
         return res
 
     def merge_by_time(self, lists, ids=None, verdicts=None):

@@ -6,6 +6,7 @@
 
 #include "dump_format.h"
 #include "uat_format.h"
+#include "sbs_in_format.h"
 
 extern "C" {
 
@@ -864,6 +865,108 @@ int mgpu_uat_encode(mgpu_ctx *c, const struct mgpu_uat_args *a) {
     }
     uat_report(a, all);
     return uat_verdict(c, a, all);
+}
+
+// ---- SBS input: decodeSbsLine over BaseStation lines (sbs_in_format.h, kernels/sbs_in.inc) ----
+
+struct SbsInCounts { uint64_t lines, consumed, recs, deferred, invalid; };
+
+// a: text, recs and line_of device pointers; a.deferred a HOST array.  The counts of this text; the deferred lines' indices (line_base
+// added) to a.deferred[listed ..] as far as deferred_cap reaches.  Overflows are the caller's to judge.
+static int sbs_decode_dev(mgpu_ctx *c, const struct mgpu_sbs_in_args &a, uint64_t line_base, uint64_t listed, SbsInCounts *n) {
+    Behind &b = *c->behind;
+    const size_t nb = (size_t) (a.nbytes / kUatTile + 2);
+    const uint64_t def_room = std::min<uint64_t>(a.deferred_cap > listed ? a.deferred_cap - listed : 0, sbs_in_max_recs(a.nbytes));   // (no more than the text can defer)
+    if (int rc = b.d_sbs_in_meta.reserve(c, nb * kBlock * sizeof(uint16_t))) return rc;
+    if (int rc = b.d_sbs_in_blocks.reserve(c, 5 * nb * sizeof(uint32_t))) return rc;
+    if (int rc = b.d_sbs_in_off.reserve(c, 3 * nb * sizeof(unsigned long long))) return rc;
+    if (int rc = b.d_sbs_in_total.reserve_exact(c, 8 * sizeof(unsigned long long))) return rc;
+    if (int rc = b.d_sbs_in_deferred.reserve(c, (def_room + 64) * sizeof(unsigned long long))) return rc;
+    const UatScratch w = {b.d_sbs_in_meta.as<uint16_t>(), b.d_sbs_in_blocks.as<uint32_t>(), b.d_sbs_in_off.as<unsigned long long>(), b.d_sbs_in_total.as<unsigned long long>(), nb};
+    const SbsInParams p = {a.text, a.nbytes, a.recs, (unsigned long long *) a.line_of, a.recs ? a.recs_cap : 0, b.d_sbs_in_deferred.as<unsigned long long>(), def_room,
+                           line_base, a.now_ms, a.source};
+    launch_sbs_decode(p, w, c->stream_aux);
+    HIPCHK(c, hipGetLastError());
+    unsigned long long total[5] = {0, 0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(total, w.total, sizeof total, hipMemcpyDeviceToHost, c->stream_aux));
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    *n = {total[0], total[1], total[2], total[3], total[4]};
+    const uint64_t fetch = std::min<uint64_t>(total[3], def_room);
+    if (fetch) HIPCHK(c, hipMemcpy(a.deferred + listed, b.d_sbs_in_deferred.p, fetch * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return MGPU_OK;
+}
+
+static bool sbs_in_args_ok(const struct mgpu_sbs_in_args *a) {
+    if (!a || a->size < sizeof(struct mgpu_sbs_in_args) || !a->consumed || !a->nlines || !a->nrecs) return false;
+    if (!sbs_in_source_ok(a->source) || a->nbytes > kUatMaxBytes || a->recs_cap > UINT64_MAX / sizeof(mgpu_sbs_rec)) return false;
+    if (a->nbytes && !a->text) return false;
+    if ((a->recs_cap && !a->recs) || (a->deferred_cap && (!a->deferred || !a->ndeferred))) return false;
+    return true;
+}
+
+static void sbs_in_report(const struct mgpu_sbs_in_args *a, const SbsInCounts &n) {
+    *a->consumed = n.consumed;
+    *a->nlines = n.lines;
+    *a->nrecs = n.recs;
+    if (a->ninvalid) *a->ninvalid = n.invalid;
+    if (a->ndeferred) *a->ndeferred = n.deferred;
+}
+
+static int sbs_in_verdict(mgpu_ctx *c, const struct mgpu_sbs_in_args *a, const SbsInCounts &n) {
+    if (n.recs > a->recs_cap) { c->err = "sbs decode: more records than the array holds"; return MGPU_E_OVERFLOW; }
+    if (n.deferred > a->deferred_cap) { c->err = "sbs decode: more deferred lines than the list holds"; return MGPU_E_OVERFLOW; }
+    return MGPU_OK;
+}
+
+int mgpu_sbs_decode_device(mgpu_ctx *c, const struct mgpu_sbs_in_args *a) {
+    if (!c || !sbs_in_args_ok(a)) return MGPU_E_INVAL;
+    if (((uintptr_t) a->recs | (uintptr_t) a->line_of) & 7u) return MGPU_E_INVAL;
+    SbsInCounts n = {0, 0, 0, 0, 0};
+    sbs_in_report(a, n);
+    if (a->nbytes == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (int rc = sbs_decode_dev(c, *a, 0, 0, &n)) return rc;
+    sbs_in_report(a, n);
+    return sbs_in_verdict(c, a, n);
+}
+
+int mgpu_sbs_decode(mgpu_ctx *c, const struct mgpu_sbs_in_args *a) {
+    if (!c || !sbs_in_args_ok(a)) return MGPU_E_INVAL;
+    SbsInCounts all = {0, 0, 0, 0, 0};
+    sbs_in_report(a, all);
+    if (a->nbytes == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    Behind &b = *c->behind;
+    uint64_t pass = std::min<uint64_t>(a->pass_bytes ? a->pass_bytes : kUatDefaultPass, a->nbytes);
+    for (uint64_t at = 0; at < a->nbytes;) {
+        const uint64_t nb = std::min<uint64_t>(pass, a->nbytes - at);
+        // what this pass may write: what the caller's arrays still hold, and no more than nb bytes of text can give
+        const uint64_t rec_room = a->recs_cap > all.recs ? std::min<uint64_t>(a->recs_cap - all.recs, sbs_in_max_recs(nb)) : 0;
+        if (int rc = b.d_sbs_in_text.reserve(c, nb + 64)) return rc;
+        if (int rc = b.d_sbs_in_recs.reserve(c, (rec_room + 1) * sizeof(mgpu_sbs_rec))) return rc;
+        struct mgpu_sbs_in_args d = *a;
+        d.text = b.d_sbs_in_text.as<uint8_t>(); d.nbytes = nb;
+        d.recs = b.d_sbs_in_recs.as<mgpu_sbs_rec>(); d.recs_cap = rec_room;
+        d.line_of = nullptr;
+        if (a->line_of) { if (int rc = b.d_sbs_in_line_of.reserve(c, (rec_room + 1) * sizeof(uint64_t))) return rc; d.line_of = b.d_sbs_in_line_of.as<uint64_t>(); }
+        HIPCHK(c, hipMemcpyAsync(b.d_sbs_in_text.p, a->text + at, nb, hipMemcpyHostToDevice, c->stream_aux));
+        SbsInCounts n;
+        if (int rc = sbs_decode_dev(c, d, all.lines, std::min<uint64_t>(all.deferred, a->deferred_cap), &n)) return rc;
+        if (n.consumed == 0 && at + nb < a->nbytes) {         // a line longer than the pass: a larger pass
+            pass = pass > a->nbytes / 2 ? a->nbytes : 2 * pass;
+            continue;
+        }
+        // (the pass stored the records below its room only: the copies stay inside the caller's arrays)
+        const uint64_t nrec = std::min<uint64_t>(n.recs, rec_room);
+        if (nrec) HIPCHK(c, hipMemcpy(a->recs + all.recs, d.recs, nrec * sizeof(mgpu_sbs_rec), hipMemcpyDeviceToHost));
+        if (nrec && a->line_of) HIPCHK(c, hipMemcpy(a->line_of + all.recs, d.line_of, nrec * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        all.lines += n.lines; all.recs += n.recs; all.deferred += n.deferred; all.invalid += n.invalid;
+        if (n.consumed == 0) break;                           // the rest has no terminator
+        at += n.consumed;
+        all.consumed = at;
+    }
+    sbs_in_report(a, all);
+    return sbs_in_verdict(c, a, all);
 }
 
 uint32_t mgpu_crc_checksum(const uint8_t *msg, int bits) { return crc_tables().checksum(msg, bits); }

@@ -308,6 +308,21 @@ struct UatScratch {
     size_t stride;                    // >= ceil(nbytes / kUatTile)
 };
 void launch_uat_encode(const UatParams &a, const UatScratch &w, hipStream_t s);
+// SBS input (kernels/sbs_in.inc; decodeSbsLine over BaseStation lines, sbs_in_format.h): the tiles, the halo and the scratch layout of
+// the UAT input; UatScratch's words per lane and per tile count records where it says frames, invalid lines where it says short lines
+struct SbsInParams {
+    const uint8_t *text;              // any alignment
+    uint64_t nbytes;
+    mgpu_sbs_rec *recs;               // nothing at or beyond recs + recs_cap is stored
+    unsigned long long *line_of;      // optional, recs_cap entries
+    uint64_t recs_cap;
+    unsigned long long *deferred;     // deferred_cap line indices
+    uint64_t deferred_cap;
+    uint64_t line_base;               // added to every line index (the host form's passes)
+    int64_t now_ms;
+    uint32_t source;
+};
+void launch_sbs_decode(const SbsInParams &a, const UatScratch &w, hipStream_t s);
 // stable merge of message lists by timestamp (kernels/merge.inc): segs [nseg] in device memory, scratch = merge_scratch_bytes(n, nseg)
 struct MergeSeg {
     const mgpu_msg *msgs;
