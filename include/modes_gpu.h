@@ -904,8 +904,8 @@ int mgpu_raw_encode_ex_device(mgpu_ctx *ctx, const struct mgpu_raw_args *args);
  *   I021/146 (:2853-2867) MCP wins over FMS, (int)altitude / 25.  I021/008 (:2870-2883) iff MGPU_OP_VALID and one of its bits (op_cc_tc & 3).
  *   I021/400 (:2886-2889) the low byte of ids[i] iff ids[i] != 0 (the array mgpu_beast_encode_ex* takes; NULL: absent).
  *   from_mlat and from_tisb are set by nothing in the reference: they suppress no record.  I021/131 and I021/295 are commented out there.
- *   A record is at most 74 bytes (I021/152 excludes I021/075 and /160).  --net-asterix-reduce (reduce_forward is the tracker's), ASTERIX
- *     input, CAT020 and sockets are not modelled.
+ *   A record is at most 74 bytes (I021/152 excludes I021/075 and /160).  --net-asterix-reduce (reduce_forward is the tracker's), CAT020
+ *     and sockets are not modelled.  ASTERIX input: mgpu_asterix_decode*, the section "ASTERIX input" below.
  *   Who gets a record (outputMessage calls the writer inside its first-message rule, :5846, with no aircraft and no correctedbits test,
  *     :5882): mgpu_raw_encode_ex's rule without MGPU_RAW_NET_RULE — verdict == NULL: every message, Mode A/C included; (v & 3) ==
  *     MGPU_GATE_FORWARD a record, MGPU_GATE_DEFER listed as {index, offset}, no record otherwise.
@@ -1260,6 +1260,116 @@ int mgpu_sbs_decode_device(mgpu_ctx *ctx, const struct mgpu_sbs_in_args *args);
 int mgpu_sbs_parse_host(const struct mgpu_sbs_in_args *args, uint64_t line_index, struct mgpu_sbs_rec *rec);
 /* The same for a line given by its bytes (without the terminator; a trailing '\r' still on it). */
 int mgpu_sbs_parse_line_host(const uint8_t *line, uint64_t len, uint32_t source, int64_t now_ms, struct mgpu_sbs_rec *rec);
+
+/* ---- ASTERIX input: CAT021 records to aircraft records (`--net-asterix-in-port`, the asterix_in connector; readAsterix,
+ *      net_io.c:4643-4659, in front of decodeAsterixMessage, :1922-2407, with readFspec :1867, readAsterixTime :1884 and
+ *      readAsterixHighPrecisionTime :1899; kernels/asterix_in.inc, csrc/asterix_in_format.h) --------------------------------------------
+ *
+ * data is a byte stream: a chain of length-prefixed records.  Framing as readAsterix's: a record starts at s, the first at 0; its
+ * length is (uint16_t)(((signed char) d[s+1] << 8) + (signed char) d[s+2]) — BOTH bytes sign-extended, as the reference's plain
+ * `char` arithmetic does on x86-64: a low byte of 0x80 or more takes 256 off, a high byte of 0x80 or more wraps through uint16_t —
+ * and the next record starts at s + len, for len 1 or 2 inside this record's own header.  Framing stops at the first of
+ *   MGPU_AST_STOP_END       fewer than 3 bytes are left at s, or s + len > nbytes: *consumed = s, the caller carries the rest over.
+ *                           DEVIATION: the reference decodes the partial record from whatever its buffer holds behind the data.
+ *   MGPU_AST_STOP_ZERO_LEN  len == 0: *consumed = s.  DEVIATION: the reference never leaves its loop on such a record.
+ *   MGPU_AST_STOP_CLOSED    a category-21 record without the I021/080 bit (fspec[1] & 0x10): the handler returns -1 and readAsterix
+ *                           closes the client (:1946-1949, :4650-4655).  *consumed = s + len; the record counts in *nframes and
+ *                           gives no record; nothing behind it is framed.
+ * and *stop says which.  *nframes: the frames consumed; those of another category count in *nother and give no record (their FSPEC
+ * is not looked at: DEVIATION where the reference's readFspec would run off its allocation, below).
+ *   Decode: one record per consumed category-21 frame, in stream order, to recs; frame_of (optional) gets the index of its frame.
+ *   The decoder starts at s + 3 and is NOT bounded by len: items that run past the record read the following bytes of the stream, as
+ *   the reference does; bytes at or beyond nbytes read as 0 (a harness of the reference must pad its buffer with zeros to agree).
+ *   readFspec follows an extension chain of any length into a 192-byte allocation; a chain of more than 191 extension bytes — the
+ *   main FSPEC, I021/040, I021/090 or I021/220 — writes outside it.  DEVIATION: such a frame gives no record and counts in
+ *   *nundefined, also where MGPU_AST_STOP_CLOSED would otherwise stop at it; so no frame is decided by more than 1 KiB behind its
+ *   start.  Bytes 0-4 of the main FSPEC, 0-1 of I021/040 and 0-2 of I021/090 are used.  The items are read in the reference's order
+ *   (:1950-2396), not the UAP's, with its skips and conditions: I021/073 + /074 are times only where sbs_pos_valid is set already;
+ *   I021/075 + /076 only where ias_valid or mach_valid is; I021/072 only where sysTimestamp is still -1; I021/155, /157, /160 are
+ *   skipped with "range exceeded"; an emitter category without a case gives category 0xE0; I021/146 needs the source bits and
+ *   alt < 0x1000; I021/210 takes the accuracy members from the I021/090 in front of it, zeros without one; I021/200 ORs 4 into
+ *   nav_modes; the callsign is valid iff all 8 characters are A-Z, '-' to '9', ' ' or '@'.  Positions are int32 * (180 / 2^23) and
+ *   int32 * (180 / 2^30) in double, the int32 the two's-complement value of the big-endian bytes; mach = raw * 0.001 in double;
+ *   ias = (unsigned)(raw * 2^-14 * 3600); gs_v0, heading, roll the double products converted to float; geom_alt, baro_rate,
+ *   geom_rate the double products converted to int.
+ *   readAsterixTime: every mstime() of a call is now_ms; (int)(raw / .128) — equal to raw * 125 / 16 in integers for every 24-bit
+ *   raw, which is what is computed —, midnight = now_ms / 86400000 * 86400000, the previous day where |midnight + t - now_ms| >
+ *   43200000.  readAsterixHighPrecisionTime's `(int)(ts / 1000) * 1000` overflows an int; what the reference's x86-64 build does is
+ *   written out: ts / 1000 truncated to 32 bits, times 1000 with 32-bit wrap-around, sign-extended to 64 bits; + 1 / - 1 (a
+ *   millisecond, as written) for FSI 1 / 2; converted to double, + offset * 2^-27, converted to uint64_t; a sum of 2^64 or more
+ *   gives 0.  sysTimestamp still -1 at the end becomes now_ms.
+ *   Not in the record, constant: remote = 1, sbs_in = 1, signalLevel = 0, receiverId = the client's.  Not modelled:
+ *   Modes.incrementId, the statistics, sockets.
+ *   args->size smaller than sizeof(struct mgpu_asterix_in_args), a NULL ctx, args, consumed, nframes, nrecs or stop, data NULL with
+ *     nbytes != 0, recs NULL with recs_cap != 0, a source above SOURCE_PRIO (11; the datasource_t `remote - 64` selects,
+ *     SOURCE_INDIRECT = 1 below 64), now_ms outside [0, 253402300800000): MGPU_E_INVAL.  nbytes == 0: MGPU_OK with zeros.  More
+ *     records than recs_cap: MGPU_E_OVERFLOW with *nrecs = what is needed; nothing is stored at or beyond the capacity.
+ *   mgpu_asterix_decode: every array in host memory; the stream goes through the library's device scratch in passes of pass_bytes
+ *     bytes (0: the library's default), each framed first and its unconsumed tail carried into the next, so the stream may be larger
+ *     than the device's memory.
+ *   mgpu_asterix_decode_device: data, recs, frame_of device pointers (data at any alignment, recs 16-byte and frame_of 8-byte
+ *     aligned); the counters in host memory in both forms.  pass_bytes is ignored; the framing scratch is about 2.5 bytes per byte. */
+#define MGPU_AST_STOP_END      0u
+#define MGPU_AST_STOP_ZERO_LEN 1u
+#define MGPU_AST_STOP_CLOSED   2u
+/* ast_flags: the valid flags mgpu_fields' `flags` has no bit for */
+#define MGPU_AST_POS_VALID       (1u << 0)   /* sbs_pos_valid */
+#define MGPU_AST_NAC_V_VALID     (1u << 1)
+#define MGPU_AST_NAC_P_VALID     (1u << 2)
+#define MGPU_AST_GVA_VALID       (1u << 3)
+#define MGPU_AST_SDA_VALID       (1u << 4)
+#define MGPU_AST_NIC_BARO_VALID  (1u << 5)
+#define MGPU_AST_OPSTATUS_VALID  (1u << 6)
+#define MGPU_AST_NAV_MODES_VALID (1u << 7)
+#define MGPU_AST_MCP_ALT_VALID   (1u << 8)
+#define MGPU_AST_FMS_ALT_VALID   (1u << 9)
+/* 128 bytes = eight 16-byte vectors; no implicit padding, and the reserved members are ZERO: records are compared bytewise. */
+struct mgpu_asterix_rec {
+    int64_t sysTimestamp;
+    double decoded_lat, decoded_lon, mach;
+    uint32_t addr;                     /* with MODES_NON_ICAO_ADDRESS (1 << 24) for ATP 3 or no I021/040 */
+    uint32_t flags;                    /* MGPU_F_BARO_ALT_VALID, _GEOM_ALT_VALID, _HEADING_VALID, _GS_VALID, _IAS_VALID, _TAS_VALID, _BARO_RATE_VALID,
+                                        * _GEOM_RATE_VALID, _SQUAWK_VALID, _CALLSIGN_VALID, _CATEGORY_VALID, _SPI_VALID, _SPI, _ALERT_VALID, _ALERT,
+                                        * _EMERGENCY_VALID, _ALT_Q_BIT, _ROLL_VALID, _MACH_VALID */
+    uint32_t ast_flags;                /* MGPU_AST_* */
+    int32_t baro_alt, geom_alt, baro_rate, geom_rate;
+    uint32_t ias, tas, squawkHex, squawkDec, category, mcp_altitude, fms_altitude;
+    float gs_v0, heading, roll;
+    char callsign[8];
+    uint8_t source, addrtype, airground, emergency, nav_modes, nac_v, nac_p, sil, sil_type, gva, sda, nic_baro, op_version, heading_type,
+            baro_alt_unit, geom_alt_unit;
+    uint8_t reserved[4];               /* 0 */
+};
+#ifdef __cplusplus
+static_assert(sizeof(struct mgpu_asterix_rec) == 128, "struct mgpu_asterix_rec");
+#else
+_Static_assert(sizeof(struct mgpu_asterix_rec) == 128, "struct mgpu_asterix_rec");
+#endif
+struct mgpu_asterix_in_args {
+    uint32_t size;                     /* sizeof(struct mgpu_asterix_in_args) */
+    uint32_t source;                   /* datasource_t, 0 .. 11: mm->source */
+    const uint8_t *data;
+    uint64_t nbytes;
+    int64_t now_ms;                    /* every mstime() of the call */
+    struct mgpu_asterix_rec *recs;     /* recs_cap entries */
+    uint64_t *frame_of;                /* optional, recs_cap entries: the frame per record, counted from the start of this call's data */
+    uint64_t recs_cap;
+    uint64_t pass_bytes;               /* host form: bytes staged per pass; 0 = the library's default */
+    uint64_t *consumed;                /* host, out */
+    uint64_t *nframes;                 /* host, out */
+    uint64_t *nrecs;                   /* host, out */
+    uint32_t *stop;                    /* host, out: MGPU_AST_STOP_* */
+    uint64_t *nother;                  /* host, out, optional */
+    uint64_t *nundefined;              /* host, out, optional */
+};
+int mgpu_asterix_decode(mgpu_ctx *ctx, const struct mgpu_asterix_in_args *args);
+int mgpu_asterix_decode_device(mgpu_ctx *ctx, const struct mgpu_asterix_in_args *args);
+/* Frame `frame_index` of a HOST-memory stream (args->data, nbytes, source, now_ms; nothing else of args is read).  Returns 1 with
+ * *rec filled, 0 for a consumed frame that gives no record (another category, undefined, the one MGPU_AST_STOP_CLOSED stops at;
+ * *rec is zeroed), or MGPU_E_INVAL (args, rec, a frame that is not consumed).  Needs no context and no GPU. */
+int mgpu_asterix_parse_host(const struct mgpu_asterix_in_args *args, uint64_t frame_index, struct mgpu_asterix_rec *rec);
+/* The same for the record that starts at `offset` (< nbytes), whether or not the chain from 0 reaches it or its length fits. */
+int mgpu_asterix_parse_record_host(const uint8_t *data, uint64_t nbytes, uint64_t offset, uint32_t source, int64_t now_ms, struct mgpu_asterix_rec *rec);
 
 #ifdef __cplusplus
 }

@@ -230,6 +230,25 @@ SBS_SOURCES = {"sbs": 3, "mlat": 4, "jaero": 6, "prio": 11}          # MGPU_SBS_
 SBS_POS_VALID, SBS_EMERGENCY_VALID, SBS_EMERGENCY = 1, 2, 4           # MGPU_SBS_*
 
 
+class AsterixInArgs(C.Structure):                                     # struct mgpu_asterix_in_args
+    _fields_ = [("size", C.c_uint32), ("source", C.c_uint32), ("data", C.c_void_p), ("nbytes", C.c_uint64), ("now_ms", C.c_int64), ("recs", C.c_void_p),
+                ("frame_of", C.c_void_p), ("recs_cap", C.c_uint64), ("pass_bytes", C.c_uint64), ("consumed", C.POINTER(C.c_uint64)),
+                ("nframes", C.POINTER(C.c_uint64)), ("nrecs", C.POINTER(C.c_uint64)), ("stop", C.POINTER(C.c_uint32)), ("nother", C.POINTER(C.c_uint64)),
+                ("nundefined", C.POINTER(C.c_uint64))]
+
+
+ASTERIX_REC_DTYPE = np.dtype([                                        # struct mgpu_asterix_rec: 128 bytes, reserved = 0
+    ("sysTimestamp", "<i8"), ("decoded_lat", "<f8"), ("decoded_lon", "<f8"), ("mach", "<f8"), ("addr", "<u4"), ("flags", "<u4"), ("ast_flags", "<u4"),
+    ("baro_alt", "<i4"), ("geom_alt", "<i4"), ("baro_rate", "<i4"), ("geom_rate", "<i4"), ("ias", "<u4"), ("tas", "<u4"), ("squawkHex", "<u4"), ("squawkDec", "<u4"),
+    ("category", "<u4"), ("mcp_altitude", "<u4"), ("fms_altitude", "<u4"), ("gs_v0", "<f4"), ("heading", "<f4"), ("roll", "<f4"), ("callsign", "S8"),
+    ("source", "u1"), ("addrtype", "u1"), ("airground", "u1"), ("emergency", "u1"), ("nav_modes", "u1"), ("nac_v", "u1"), ("nac_p", "u1"), ("sil", "u1"),
+    ("sil_type", "u1"), ("gva", "u1"), ("sda", "u1"), ("nic_baro", "u1"), ("op_version", "u1"), ("heading_type", "u1"), ("baro_alt_unit", "u1"),
+    ("geom_alt_unit", "u1"), ("reserved", "u1", 4)])
+assert ASTERIX_REC_DTYPE.itemsize == 128
+AST_STOP_END, AST_STOP_ZERO_LEN, AST_STOP_CLOSED = 0, 1, 2            # MGPU_AST_STOP_*
+AST_POS_VALID = 1                                                     # MGPU_AST_POS_VALID
+
+
 ABI_VERSION = 6                             # MGPU_ABI_VERSION of the include/modes_gpu.h these ctypes mirrors were written against
 
 
@@ -422,6 +441,10 @@ def load_library():
     lib.mgpu_sbs_decode.argtypes = [vp, C.POINTER(SbsInArgs)]
     lib.mgpu_sbs_decode_device.argtypes = [vp, C.POINTER(SbsInArgs)]
     lib.mgpu_sbs_parse_host.argtypes = [C.POINTER(SbsInArgs), u64, vp]
+    lib.mgpu_asterix_decode.argtypes = [vp, C.POINTER(AsterixInArgs)]
+    lib.mgpu_asterix_decode_device.argtypes = [vp, C.POINTER(AsterixInArgs)]
+    lib.mgpu_asterix_parse_host.argtypes = [C.POINTER(AsterixInArgs), u64, vp]
+    lib.mgpu_asterix_parse_record_host.argtypes = [vp, u64, u64, C.c_uint32, C.c_int64, vp]
     lib.mgpu_sbs_parse_line_host.argtypes = [vp, u64, C.c_uint32, C.c_int64, vp]
     lib.mgpu_snip.argtypes = [vp, C.POINTER(SnipArgs)]
     lib.mgpu_snip_device.argtypes = [vp, C.POINTER(SnipArgs)]
@@ -1068,6 +1091,29 @@ class Demodulator:
                 where = np.searchsorted(res["line_of"], np.array(extra_lines, dtype=np.uint64))
                 res.update(recs=np.insert(res["recs"], where, np.concatenate(extra_recs)), line_of=np.insert(res["line_of"], where, np.array(extra_lines, dtype=np.uint64)))
         return res
+
+    def asterix_decode(self, data, source=1, now_ms=0, pass_bytes=0):
+        """mgpu_asterix_decode on a host byte string of ASTERIX records (`--net-asterix-in-port`): one record per category-21 frame
+        with an address, the reference's decodeAsterixMessage member for member.  source: the reference's datasource_t (1:
+        SOURCE_INDIRECT).  Two calls: the first counts, the second fills arrays of that size.
+        -> dict(recs, frame_of, consumed, nframes, nother, nundefined, stop)."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        c = [C.c_uint64(0) for _ in range(5)]
+        stop = C.c_uint32(0)
+
+        def call(recs, frame_of, cap):
+            a = AsterixInArgs(C.sizeof(AsterixInArgs), int(source), buf.ctypes.data if buf.size else None, buf.size, int(now_ms), recs, frame_of, cap, int(pass_bytes),
+                              C.pointer(c[0]), C.pointer(c[1]), C.pointer(c[2]), C.pointer(stop), C.pointer(c[3]), C.pointer(c[4]))
+            return int(self.lib.mgpu_asterix_decode(self.ctx, C.byref(a)))
+        rc = call(None, None, 0)
+        if rc not in (0, -5):                               # MGPU_E_OVERFLOW: *nrecs is what is needed
+            self._chk(rc, "mgpu_asterix_decode")
+        n = int(c[2].value)
+        recs, frame_of = np.zeros(n, dtype=ASTERIX_REC_DTYPE), np.zeros(n, dtype=np.uint64)
+        if n:
+            self._chk(call(recs.ctypes.data, frame_of.ctypes.data, n), "mgpu_asterix_decode")
+        return dict(recs=recs, frame_of=frame_of, consumed=int(c[0].value), nframes=int(c[1].value), nother=int(c[3].value), nundefined=int(c[4].value),
+                    stop=int(stop.value))
 
     def merge_by_time(self, lists, ids=None, verdicts=None):
         """mgpu_merge_by_time on host arrays: the receivers' lists merged by timestamp on the GPU, equal stamps in input order —

@@ -7,6 +7,7 @@
 #include "dump_format.h"
 #include "uat_format.h"
 #include "sbs_in_format.h"
+#include "asterix_in_format.h"
 
 extern "C" {
 
@@ -967,6 +968,111 @@ int mgpu_sbs_decode(mgpu_ctx *c, const struct mgpu_sbs_in_args *a) {
     }
     sbs_in_report(a, all);
     return sbs_in_verdict(c, a, all);
+}
+
+// ---- ASTERIX input: readAsterix + decodeAsterixMessage over a length-chained stream (asterix_in_format.h, kernels/asterix_in.inc) ----
+
+struct AstInCounts { uint64_t frames, recs, other, undefined, consumed; uint32_t stop; };
+
+// a: data, recs and frame_of device pointers; `look` bytes behind a.nbytes are the stream's too.  The counts of this stretch.
+// Overflows are the caller's to judge.
+static int asterix_decode_dev(mgpu_ctx *c, const struct mgpu_asterix_in_args &a, uint64_t look, uint64_t frame_base, AstInCounts *n) {
+    Behind &b = *c->behind;
+    const size_t tiles = ast_in_tiles(a.nbytes), groups = ast_in_groups(a.nbytes);
+    if (int rc = b.d_ast_in_maps.reserve(c, (uint64_t) tiles * kAstTile * sizeof(uint16_t))) return rc;
+    if (int rc = b.d_ast_in_gmaps.reserve(c, (uint64_t) groups * kAstTile * sizeof(uint16_t))) return rc;
+    if (int rc = b.d_ast_in_entry.reserve(c, (tiles + groups) * sizeof(uint32_t))) return rc;
+    if (int rc = b.d_ast_in_bits.reserve(c, 3 * (uint64_t) tiles * kAstWords * sizeof(uint32_t))) return rc;
+    if (int rc = b.d_ast_in_blocks.reserve(c, 4 * tiles * sizeof(uint32_t))) return rc;
+    if (int rc = b.d_ast_in_off.reserve(c, 2 * tiles * sizeof(unsigned long long))) return rc;
+    if (int rc = b.d_ast_in_total.reserve_exact(c, 16 * sizeof(unsigned long long))) return rc;
+    const AstInScratch w = {b.d_ast_in_maps.as<uint16_t>(), b.d_ast_in_gmaps.as<uint16_t>(), b.d_ast_in_entry.as<uint32_t>(), b.d_ast_in_bits.as<uint32_t>(),
+                            b.d_ast_in_blocks.as<uint32_t>(), b.d_ast_in_off.as<unsigned long long>(), b.d_ast_in_total.as<unsigned long long>(), tiles};
+    const AstInParams p = {a.data, a.nbytes, look, a.recs, (unsigned long long *) a.frame_of, a.recs ? a.recs_cap : 0, frame_base, a.now_ms, a.source};
+    launch_asterix_decode(p, w, c->stream_aux);
+    HIPCHK(c, hipGetLastError());
+    unsigned long long total[6] = {0, 0, 0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(total, w.total, sizeof total, hipMemcpyDeviceToHost, c->stream_aux));
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    *n = {total[0], total[1], total[2], total[3], total[4], (uint32_t) total[5]};
+    return MGPU_OK;
+}
+
+static bool asterix_in_args_ok(const struct mgpu_asterix_in_args *a) {
+    if (!a || a->size < sizeof(struct mgpu_asterix_in_args) || !a->consumed || !a->nframes || !a->nrecs || !a->stop) return false;
+    if (!ast_in_source_ok(a->source) || !ast_in_now_ok(a->now_ms) || a->nbytes > kAstMaxBytes || a->recs_cap > UINT64_MAX / sizeof(mgpu_asterix_rec)) return false;
+    if (a->nbytes && !a->data) return false;
+    if (a->recs_cap && !a->recs) return false;
+    return true;
+}
+
+static void asterix_in_report(const struct mgpu_asterix_in_args *a, const AstInCounts &n) {
+    *a->consumed = n.consumed;
+    *a->nframes = n.frames;
+    *a->nrecs = n.recs;
+    *a->stop = n.stop;
+    if (a->nother) *a->nother = n.other;
+    if (a->nundefined) *a->nundefined = n.undefined;
+}
+
+static int asterix_in_verdict(mgpu_ctx *c, const struct mgpu_asterix_in_args *a, const AstInCounts &n) {
+    if (n.recs > a->recs_cap) { c->err = "asterix decode: more records than the array holds"; return MGPU_E_OVERFLOW; }
+    return MGPU_OK;
+}
+
+int mgpu_asterix_decode_device(mgpu_ctx *c, const struct mgpu_asterix_in_args *a) {
+    if (!c || !asterix_in_args_ok(a)) return MGPU_E_INVAL;
+    if (((uintptr_t) a->recs & 15u) || ((uintptr_t) a->frame_of & 7u)) return MGPU_E_INVAL;
+    AstInCounts n = {0, 0, 0, 0, 0, MGPU_AST_STOP_END};
+    asterix_in_report(a, n);
+    if (a->nbytes == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (int rc = asterix_decode_dev(c, *a, 0, 0, &n)) return rc;
+    asterix_in_report(a, n);
+    return asterix_in_verdict(c, a, n);
+}
+
+constexpr uint64_t kAstInDefaultPass = 16ull << 20;          // bytes the host form stages per pass, pass_bytes == 0
+
+int mgpu_asterix_decode(mgpu_ctx *c, const struct mgpu_asterix_in_args *a) {
+    if (!c || !asterix_in_args_ok(a)) return MGPU_E_INVAL;
+    AstInCounts all = {0, 0, 0, 0, 0, MGPU_AST_STOP_END};
+    asterix_in_report(a, all);
+    if (a->nbytes == 0) return MGPU_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    Behind &b = *c->behind;
+    uint64_t pass = std::min<uint64_t>(a->pass_bytes ? a->pass_bytes : kAstInDefaultPass, a->nbytes);
+    for (uint64_t at = 0;;) {
+        // a pass frames nb bytes; its items may read kAstInLook more, which decide every frame that starts inside the pass
+        const uint64_t nb = std::min<uint64_t>(pass, a->nbytes - at), look = std::min<uint64_t>(kAstInLook, a->nbytes - at - nb);
+        const uint64_t rec_room = a->recs_cap > all.recs ? std::min<uint64_t>(a->recs_cap - all.recs, ast_in_max_recs(nb)) : 0;
+        if (int rc = b.d_ast_in_data.reserve(c, nb + look + 64)) return rc;
+        if (int rc = b.d_ast_in_recs.reserve(c, (rec_room + 1) * sizeof(mgpu_asterix_rec))) return rc;
+        struct mgpu_asterix_in_args d = *a;
+        d.data = b.d_ast_in_data.as<uint8_t>(); d.nbytes = nb;
+        d.recs = b.d_ast_in_recs.as<mgpu_asterix_rec>(); d.recs_cap = rec_room;
+        d.frame_of = nullptr;
+        if (a->frame_of) { if (int rc = b.d_ast_in_frame_of.reserve(c, (rec_room + 1) * sizeof(uint64_t))) return rc; d.frame_of = b.d_ast_in_frame_of.as<uint64_t>(); }
+        HIPCHK(c, hipMemcpyAsync(b.d_ast_in_data.p, a->data + at, nb + look, hipMemcpyHostToDevice, c->stream_aux));
+        AstInCounts n;
+        if (int rc = asterix_decode_dev(c, d, look, all.frames, &n)) return rc;
+        const bool last = at + nb == a->nbytes;
+        if (n.consumed == 0 && n.stop == MGPU_AST_STOP_END && !last) {   // a record longer than the pass: a larger pass
+            pass = pass > a->nbytes / 2 ? a->nbytes : 2 * pass;
+            continue;
+        }
+        // (the pass stored the records below its room only: the copies stay inside the caller's arrays)
+        const uint64_t nrec = std::min<uint64_t>(n.recs, rec_room);
+        if (nrec) HIPCHK(c, hipMemcpy(a->recs + all.recs, d.recs, nrec * sizeof(mgpu_asterix_rec), hipMemcpyDeviceToHost));
+        if (nrec && a->frame_of) HIPCHK(c, hipMemcpy(a->frame_of + all.recs, d.frame_of, nrec * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        all.frames += n.frames; all.recs += n.recs; all.other += n.other; all.undefined += n.undefined;
+        at += n.consumed;
+        all.consumed = at;
+        all.stop = n.stop;
+        if (n.stop != MGPU_AST_STOP_END || last) break;             // the unconsumed tail is the next pass's head
+    }
+    asterix_in_report(a, all);
+    return asterix_in_verdict(c, a, all);
 }
 
 uint32_t mgpu_crc_checksum(const uint8_t *msg, int bits) { return crc_tables().checksum(msg, bits); }

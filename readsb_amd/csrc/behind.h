@@ -48,7 +48,10 @@ struct Behind {
     DevBuf d_uat_meta, d_uat_blocks, d_uat_off, d_uat_total, d_uat_deferred, d_uat_sig_table, d_uat_in, d_uat_out, d_uat_msgs, d_uat_sig, d_uat_line_of;
     // SBS input (kernels/sbs_in.inc): the UAT input's scratch layout in buffers of its own; the host-array form's staged text and its results
     DevBuf d_sbs_in_meta, d_sbs_in_blocks, d_sbs_in_off, d_sbs_in_total, d_sbs_in_deferred, d_sbs_in_text, d_sbs_in_recs, d_sbs_in_line_of;
-    DevBuf d_roll_tan;                                       // tables.h build_roll_tangent_table(), uploaded on first use
+    // ASTERIX input (kernels/asterix_in.inc): the tiles' and the groups' exit maps; the entries; three bitmaps per tile; per tile four
+    // words and two offsets; the nine totals; the host-array form's staged stream and its results
+    DevBuf d_ast_in_maps, d_ast_in_gmaps, d_ast_in_entry, d_ast_in_bits, d_ast_in_blocks, d_ast_in_off, d_ast_in_total, d_ast_in_data, d_ast_in_recs, d_ast_in_frame_of;
+    DevBuf d_roll_tan;                                      // tables.h build_roll_tangent_table(), uploaded on first use
     // the first-stage tracking gate (kernels/gate.inc): the aircraft table (1 GiB, allocated and zeroed by the first call), its scratch,
     // the host-array forms' verdicts
     DevBuf d_gate_table, d_gate_scratch, d_gate_verdict;

@@ -323,6 +323,35 @@ struct SbsInParams {
     uint32_t source;
 };
 void launch_sbs_decode(const SbsInParams &a, const UatScratch &w, hipStream_t s);
+// ASTERIX input (kernels/asterix_in.inc; readAsterix + decodeAsterixMessage over a length-chained stream, asterix_in_format.h)
+constexpr uint32_t kAstTile = 65536;          // bytes per tile: a length is below 65536, so a chain that enters tile t leaves it into tile t + 1
+constexpr uint32_t kAstGroup = 32;            // tiles whose exit maps are composed into one
+constexpr uint32_t kAstWords = kAstTile / 32; // words of a tile's bitmap, a bit per byte
+constexpr uint64_t kAstMaxBytes = (uint64_t) kAstTile * 0x7ffffffeull;   // a grid's limit
+constexpr size_t ast_in_tiles(uint64_t nbytes) { return (size_t) (nbytes / kAstTile + 1); }   // (the chain may end AT nbytes)
+constexpr size_t ast_in_groups(uint64_t nbytes) { return (ast_in_tiles(nbytes) + kAstGroup - 1) / kAstGroup; }
+struct AstInParams {
+    const uint8_t *data;              // any alignment
+    uint64_t nbytes;                  // what is framed
+    uint64_t look;                    // bytes behind them an item that overruns its record may read (the host form's passes)
+    mgpu_asterix_rec *recs;           // 16-byte aligned; nothing at or beyond recs + recs_cap is stored
+    unsigned long long *frame_of;     // optional, recs_cap entries
+    uint64_t recs_cap;
+    uint64_t frame_base;              // added to every frame index (the host form's passes)
+    int64_t now_ms;
+    uint32_t source;
+};
+struct AstInScratch {
+    uint16_t *maps;                   // [(tiles - 1) * kAstTile] a tile's exit map: entry offset -> entry offset of the next tile, 0xffff: the chain ends here
+    uint16_t *gmaps;                  // [(groups - 1) * kAstTile] the same over a group of tiles
+    uint32_t *entry;                  // [tiles + groups] where the chain from 0 enters each tile (kNone: it does not), then each group
+    uint32_t *bits;                   // [3 * tiles * kAstWords] per tile: frame starts | those that give a record | those of another category
+    uint32_t *blocks;                 // [4 * stride] per tile: frames | records | other | undefined
+    unsigned long long *off;          // [2 * stride] the exclusive prefix sums of the first two
+    unsigned long long *total;        // [9] frames, records, other, undefined, consumed, stop | the first closing frame (~0: none), the chain's end, its kind
+    size_t stride;                    // >= tiles
+};
+void launch_asterix_decode(const AstInParams &a, const AstInScratch &w, hipStream_t s);
 // stable merge of message lists by timestamp (kernels/merge.inc): segs [nseg] in device memory, scratch = merge_scratch_bytes(n, nseg)
 struct MergeSeg {
     const mgpu_msg *msgs;
