@@ -1371,6 +1371,91 @@ int mgpu_asterix_parse_host(const struct mgpu_asterix_in_args *args, uint64_t fr
 /* The same for the record that starts at `offset` (< nbytes), whether or not the chain from 0 reaches it or its length fits. */
 int mgpu_asterix_parse_record_host(const uint8_t *data, uint64_t nbytes, uint64_t offset, uint32_t source, int64_t now_ms, struct mgpu_asterix_rec *rec);
 
+/* ---- Raw input: AVR lines to accepted message records (`--net-ri-port`, 30001 by convention; processHexMessage -> decodeHexMessage,
+ * net_io.c:4104-4317, behind readAscii, :4599-4641; the front of decodeModesMessage, mode_s.c:443-606, and its icaoFilterAdd,
+ * :766-779; kernels/raw_in.inc, raw_in_format.h) ---------------------------------------------------------------------------------
+ * A stream of AVR lines — what mgpu_raw_encode_ex and readsb_gpu_fanin --out-prefix write, and the Aerobits form — to the messages
+ * decodeHexMessage hands to netUseMessage, the counters it keeps, and the context's ICAO filter moved to where the reference's
+ * stands after the stream.
+ *   Lines (readAscii :4609-4631): a line ends at '\n' or at a NUL byte; one '\r' in front of the terminator is removed where
+ *     `p - 1 > som`.  Bytes behind the last terminator are not consumed.
+ *   A line (decodeHexMessage :4116-4262): isspace trimmed on both sides; the Aerobits suffix "(SIGS,SIGQ,TS)" (:4129-4165: strtok_r on
+ *     ",", strtol base 10 and 16, the int truncation of after_pps, the second rollback, now * 12e3, signalLevel = fmin(1, (mV/1000)^2));
+ *     the ';' (:4173) and length (:4177) checks; the lead characters '<', '@', '%', '*', ':' (:4180-4243) — the 12 timestamp digits
+ *     are shifted onto what the suffix left, a non-hex digit contributes -1; the three legal lengths (:4245-4249), Mode A/C only with
+ *     cfg.mode_ac (:4251-4254), the hex check (:4256-4262).
+ *   The decode (mode_s.c:443-606): the all-zero test, the DF, fixDF17msgtype (:276-301) under cfg.fixDF && cfg.nfix_crc, the length by
+ *     DF, the syndrome, per DF modesChecksumDiagnose / modesChecksumFix with the context's tables.  A DF0/4/5/16/20/21/24-31 frame, a
+ *     repaired DF11 and a DF17/18 whose repair changed the address are accepted iff their address is in the ICAO filter AS IT STANDS
+ *     AT THAT LINE: the filter at the start of the call, plus the clean DF17 and clean DF11-IID-0 lines in front of it (:766-779),
+ *     minus what the first growth of the table drops (icaoFilterResize re-inserts the active generation only, icao_filter.c:65-93).
+ *     The device resolves that in parallel and exactly; afterwards the context's filter holds the new addresses, in the
+ *     reference's order, and the demodulator's pre-screen knows them (as after mgpu_filter_add).  The calls drain the pipeline first.
+ *   A record: timestamp as parsed, sysTimestamp = now_ms, score 0, phase 0, correctedbits / msgtype / msgbits after the decode, addr =
+ *     AA after the fix for DF11/17/18 and the syndrome otherwise, msg the corrected frame, raw the frame as received.  sig_len 1 and
+ *     sig_sumsq = (257 b)^2 with b the beast signal byte the reference would write for mm->signalLevel (the byte of a '<' line; 0
+ *     where the line carries no signal); signal_level[] receives mm->signalLevel itself, bit for bit, and is the authority.  A Mode
+ *     A/C line gives msgtype 77, msgbits 16, addr = ModeA & 0xFF7F (decodeModeAMessage, mode_ac.c:165-200), like the demodulator's.
+ *   line_class (optional): one byte per line of the stream, MGPU_RAW_*, the filter's verdict resolved.
+ *   counters: Modes.stats_current.remote_received_modes, _modeac, remote_rejected_unknown_icao, remote_rejected_bad and
+ *     remote_accepted[0..2] (:4268-4283), of this call.
+ *   Not modelled: what follows in decodeModesMessage for remote messages (the MLAT / SBS / garbage overrides, mode_s.c:781-799, which
+ *     follow from timestamp and addr); netUseMessage and beyond.  Departures: an empty line (the reference reads the byte in front of
+ *     it, hex[l - 1] with l == 0) and a line longer than 256 bytes are "not a frame".
+ *   args->size smaller than sizeof(struct mgpu_raw_in_args), a NULL ctx, args, consumed, nlines, nmsgs or counters, text NULL with
+ *     nbytes != 0, msgs NULL with msgs_cap != 0, line_class NULL with line_class_cap != 0, now_ms outside [0, 253402300800000):
+ *     MGPU_E_INVAL.  nbytes == 0: MGPU_OK with zeros.  More messages than msgs_cap, or (with line_class) more lines than
+ *     line_class_cap: MGPU_E_OVERFLOW with *nmsgs and *nlines = what is needed; nothing is stored at or beyond a capacity and the
+ *     filter is left untouched.
+ *   mgpu_raw_decode: every array in host memory; the text goes through device scratch in passes of pass_bytes bytes (0: the library's
+ *     default) cut at line ends; the filter state carries from pass to pass (and on MGPU_E_OVERFLOW in any pass goes back to where
+ *     it stood before the call).  nbytes < 2^32 in this form too: line indices are 32 bits on the device.
+ *   mgpu_raw_decode_device: text, msgs, line_of, signal_level, line_class device pointers (text at any alignment; msgs, line_of and
+ *     signal_level 8-byte aligned); the counts are in host memory.  nbytes < 2^32.  pass_bytes is ignored. */
+#define MGPU_RAW_NONE     0u   /* not a frame: decodeHexMessage returned 0 before the decode */
+#define MGPU_RAW_MODEAC   1u   /* a Mode A/C record (accepted) */
+#define MGPU_RAW_BAD      2u   /* rejected bad, decodeModesMessage -2 */
+#define MGPU_RAW_ACCEPT   3u   /* accepted */
+#define MGPU_RAW_COND     4u   /* mgpu_raw_parse_line_host only: accepted iff addr is in the filter */
+#define MGPU_RAW_UNKNOWN  5u   /* rejected unknown ICAO, decodeModesMessage -1 */
+struct mgpu_raw_in_counters {
+    uint64_t remote_received_modes, remote_received_modeac, remote_rejected_unknown_icao, remote_rejected_bad, remote_accepted[3];
+};
+struct mgpu_raw_in_config {
+    uint32_t size;                     /* sizeof(struct mgpu_raw_in_config) */
+    int32_t nfix_crc, fixDF;           /* as in struct mgpu_config */
+    uint32_t mode_ac;
+};
+struct mgpu_raw_in_line {              /* 88 bytes */
+    struct mgpu_msg msg;               /* zero unless cls is MGPU_RAW_MODEAC, _ACCEPT or _COND */
+    double signal_level;
+    uint32_t cls;                      /* MGPU_RAW_NONE, _MODEAC, _BAD, _ACCEPT or _COND */
+    uint32_t addr;                     /* the address the filter is asked about (_COND) or learns (adder) */
+    uint32_t adder;                    /* 1: a clean DF17 or a clean DF11 with IID 0 — icaoFilterAdd(addr), mode_s.c:766-779 */
+    uint32_t reserved;                 /* 0 */
+};
+struct mgpu_raw_in_args {
+    uint32_t size, reserved;           /* sizeof(struct mgpu_raw_in_args), 0 */
+    const uint8_t *text;
+    uint64_t nbytes;
+    int64_t now_ms;
+    struct mgpu_msg *msgs;             /* msgs_cap entries: the accepted messages in line order */
+    uint64_t *line_of;                 /* optional, msgs_cap entries: the source line per message */
+    double *signal_level;              /* optional, msgs_cap entries: mm->signalLevel */
+    uint64_t msgs_cap;
+    uint8_t *line_class;               /* optional, line_class_cap entries: MGPU_RAW_* per line */
+    uint64_t line_class_cap;
+    uint64_t *consumed, *nlines, *nmsgs;   /* host, out */
+    struct mgpu_raw_in_counters *counters;   /* host, out */
+    uint64_t pass_bytes;               /* host form: bytes staged per pass; 0 = the library's default */
+};
+int mgpu_raw_decode(mgpu_ctx *ctx, const struct mgpu_raw_in_args *args);          /* every array in host memory, text staged in passes cut at line ends */
+int mgpu_raw_decode_device(mgpu_ctx *ctx, const struct mgpu_raw_in_args *args);   /* text, msgs, line_of, signal_level, line_class device pointers */
+/* One line given by its bytes (without the terminator; a trailing '\r' still on it) parsed on the host by the same parser, the CRC
+ * tables of cfg->nfix_crc built once per value.  Returns 1 with *out filled (cls != MGPU_RAW_NONE), 0 for a line that is not a
+ * frame (*out zeroed), or MGPU_E_INVAL.  Needs no context and no GPU. */
+int mgpu_raw_parse_line_host(const uint8_t *line, uint64_t len, int64_t now_ms, const struct mgpu_raw_in_config *cfg, struct mgpu_raw_in_line *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -230,6 +230,34 @@ SBS_SOURCES = {"sbs": 3, "mlat": 4, "jaero": 6, "prio": 11}          # MGPU_SBS_
 SBS_POS_VALID, SBS_EMERGENCY_VALID, SBS_EMERGENCY = 1, 2, 4           # MGPU_SBS_*
 
 
+class RawInCounters(C.Structure):                                     # struct mgpu_raw_in_counters
+    _fields_ = [("remote_received_modes", C.c_uint64), ("remote_received_modeac", C.c_uint64), ("remote_rejected_unknown_icao", C.c_uint64),
+                ("remote_rejected_bad", C.c_uint64), ("remote_accepted", C.c_uint64 * 3)]
+
+
+class RawInArgs(C.Structure):                                         # struct mgpu_raw_in_args
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_uint32), ("text", C.c_void_p), ("nbytes", C.c_uint64), ("now_ms", C.c_int64), ("msgs", C.c_void_p),
+                ("line_of", C.c_void_p), ("signal_level", C.c_void_p), ("msgs_cap", C.c_uint64), ("line_class", C.c_void_p), ("line_class_cap", C.c_uint64),
+                ("consumed", C.POINTER(C.c_uint64)), ("nlines", C.POINTER(C.c_uint64)), ("nmsgs", C.POINTER(C.c_uint64)), ("counters", C.POINTER(RawInCounters)),
+                ("pass_bytes", C.c_uint64)]
+
+
+class RawInConfig(C.Structure):                                       # struct mgpu_raw_in_config
+    _fields_ = [("size", C.c_uint32), ("nfix_crc", C.c_int32), ("fixDF", C.c_int32), ("mode_ac", C.c_uint32)]
+
+
+class RawInLine(C.Structure):                                         # struct mgpu_raw_in_line: 88 bytes
+    _fields_ = [("msg", C.c_uint8 * 64), ("signal_level", C.c_double), ("cls", C.c_uint32), ("addr", C.c_uint32), ("adder", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RawInFilter(C.Structure):                                       # struct mgpu_raw_in_filter
+    _fields_ = [("gen_active", C.c_void_p), ("gen_inactive", C.c_void_p), ("n_active", C.c_uint64), ("n_inactive", C.c_uint64), ("occupied", C.c_uint32),
+                ("table_bits", C.c_uint32)]
+
+
+RAW_NONE, RAW_MODEAC, RAW_BAD, RAW_ACCEPT, RAW_COND, RAW_UNKNOWN = range(6)   # MGPU_RAW_*
+
+
 class AsterixInArgs(C.Structure):                                     # struct mgpu_asterix_in_args
     _fields_ = [("size", C.c_uint32), ("source", C.c_uint32), ("data", C.c_void_p), ("nbytes", C.c_uint64), ("now_ms", C.c_int64), ("recs", C.c_void_p),
                 ("frame_of", C.c_void_p), ("recs_cap", C.c_uint64), ("pass_bytes", C.c_uint64), ("consumed", C.POINTER(C.c_uint64)),
@@ -441,6 +469,10 @@ def load_library():
     lib.mgpu_sbs_decode.argtypes = [vp, C.POINTER(SbsInArgs)]
     lib.mgpu_sbs_decode_device.argtypes = [vp, C.POINTER(SbsInArgs)]
     lib.mgpu_sbs_parse_host.argtypes = [C.POINTER(SbsInArgs), u64, vp]
+    lib.mgpu_raw_decode.argtypes = [vp, C.POINTER(RawInArgs)]
+    lib.mgpu_raw_decode_device.argtypes = [vp, C.POINTER(RawInArgs)]
+    lib.mgpu_raw_parse_line_host.argtypes = [vp, u64, C.c_int64, C.POINTER(RawInConfig), C.POINTER(RawInLine)]
+    lib.mgpu_raw_decode_host.argtypes = [C.POINTER(RawInArgs), C.POINTER(RawInConfig), C.POINTER(RawInFilter)]
     lib.mgpu_asterix_decode.argtypes = [vp, C.POINTER(AsterixInArgs)]
     lib.mgpu_asterix_decode_device.argtypes = [vp, C.POINTER(AsterixInArgs)]
     lib.mgpu_asterix_parse_host.argtypes = [C.POINTER(AsterixInArgs), u64, vp]
@@ -1091,6 +1123,27 @@ class Demodulator:
                 where = np.searchsorted(res["line_of"], np.array(extra_lines, dtype=np.uint64))
                 res.update(recs=np.insert(res["recs"], where, np.concatenate(extra_recs)), line_of=np.insert(res["line_of"], where, np.array(extra_lines, dtype=np.uint64)))
         return res
+
+    def raw_decode(self, text, now_ms=0, pass_bytes=0):
+        """mgpu_raw_decode on a host byte string of AVR lines (`--net-ri-port`): the messages the reference's decodeHexMessage accepts,
+        in line order, the ICAO filter's answers as they stand at every line; the context's filter learns the stream's clean DF17 /
+        DF11 addresses, and the demodulator on this context sees them.
+        -> dict(msgs, line_of, signal_level, line_class, consumed, nlines, counters)."""
+        buf = np.frombuffer(bytes(text), dtype=np.uint8)
+        most = buf.size // 6 + 1                            # a frame line needs 5 bytes and a terminator (raw_in_format.h)
+        msgs, line_of, signal = np.zeros(most, dtype=MSG_DTYPE), np.empty(most, dtype=np.uint64), np.empty(most, dtype=np.float64)
+        cls = np.zeros(buf.size + 1, dtype=np.uint8)
+        c = [C.c_uint64(0) for _ in range(3)]
+        cn = RawInCounters()
+        a = RawInArgs(C.sizeof(RawInArgs), 0, buf.ctypes.data if buf.size else None, buf.size, int(now_ms), msgs.ctypes.data, line_of.ctypes.data, signal.ctypes.data, most,
+                      cls.ctypes.data, cls.size, *[C.pointer(x) for x in c], C.pointer(cn), int(pass_bytes))
+        self._chk(self.lib.mgpu_raw_decode(self.ctx, C.byref(a)), "mgpu_raw_decode")
+        consumed, nlines, n = (int(x.value) for x in c)
+        counters = dict(remote_received_modes=int(cn.remote_received_modes), remote_received_modeac=int(cn.remote_received_modeac),
+                        remote_rejected_unknown_icao=int(cn.remote_rejected_unknown_icao), remote_rejected_bad=int(cn.remote_rejected_bad),
+                        remote_accepted=[int(x) for x in cn.remote_accepted])
+        return dict(msgs=msgs[:n].copy(), line_of=line_of[:n].copy(), signal_level=signal[:n].copy(), line_class=cls[:nlines].copy(), consumed=consumed, nlines=nlines,
+                    counters=counters)
 
     def asterix_decode(self, data, source=1, now_ms=0, pass_bytes=0):
         """mgpu_asterix_decode on a host byte string of ASTERIX records (`--net-asterix-in-port`): one record per category-21 frame

@@ -7,6 +7,7 @@
 #include "dump_format.h"
 #include "uat_format.h"
 #include "sbs_in_format.h"
+#include "raw_in_format.h"
 #include "asterix_in_format.h"
 
 extern "C" {
@@ -968,6 +969,226 @@ int mgpu_sbs_decode(mgpu_ctx *c, const struct mgpu_sbs_in_args *a) {
     }
     sbs_in_report(a, all);
     return sbs_in_verdict(c, a, all);
+}
+
+// ---- Raw input: decodeHexMessage + the front of decodeModesMessage over AVR lines (raw_in_format.h, kernels/raw_in.inc) ----
+
+struct RawInCounts {
+    uint64_t lines = 0, consumed = 0, msgs = 0;
+    uint64_t cn[7] = {0, 0, 0, 0, 0, 0, 0};
+};
+
+// a: text, msgs, line_of, signal_level, line_class device pointers, the capacities what this text may store (line_class indexed by
+// this text's own lines).  The counts of this text; the context's filter moved on by the text's new adds, which are appended to
+// *adds (the caller publishes them to the pre-screen's bitmap, or puts the filter back).
+static int raw_decode_passes(mgpu_ctx *c, const struct mgpu_raw_in_args &a, uint64_t line_base, RawInCounts *n, std::vector<uint32_t> *adds) {
+    Behind &b = *c->behind;
+    const size_t nb = (size_t) (a.nbytes / kUatTile + 2);
+    const uint64_t cand_cap = raw_in_max_cands(a.nbytes), ncb = cand_cap / kBlock + 1;
+    if (int rc = b.d_raw_in_meta.reserve(c, nb * kBlock * sizeof(uint16_t))) return rc;
+    if (int rc = b.d_raw_in_blocks.reserve(c, 5 * nb * sizeof(uint32_t))) return rc;
+    if (int rc = b.d_raw_in_off.reserve(c, 3 * nb * sizeof(unsigned long long))) return rc;
+    if (int rc = b.d_raw_in_total.reserve_exact(c, 8 * sizeof(unsigned long long))) return rc;
+    if (int rc = b.d_raw_in_cand_rec.reserve(c, cand_cap * sizeof(mgpu_msg))) return rc;
+    if (int rc = b.d_raw_in_cand_sig.reserve(c, cand_cap * sizeof(double))) return rc;
+    if (int rc = b.d_raw_in_cand_line.reserve(c, cand_cap * sizeof(uint32_t))) return rc;
+    if (int rc = b.d_raw_in_cand_meta.reserve(c, cand_cap * sizeof(uint32_t))) return rc;
+    if (int rc = b.d_raw_in_new_adds.reserve(c, cand_cap * sizeof(uint32_t))) return rc;
+    if (int rc = b.d_raw_in_cb.reserve(c, 8 * ncb * sizeof(uint32_t))) return rc;
+    if (int rc = b.d_raw_in_co.reserve(c, 2 * ncb * sizeof(unsigned long long))) return rc;
+    if (int rc = b.d_raw_in_misc.reserve_exact(c, 16 * sizeof(unsigned long long))) return rc;
+    if (!b.d_raw_in_first.p) {                                  // the tables, once: first[] all ones, the bitmaps zero, the CRC's bytes
+        if (int rc = b.d_raw_in_first.reserve_exact(c, (uint64_t) sizeof(uint32_t) << 24)) return rc;
+        HIPCHK(c, hipMemsetAsync(b.d_raw_in_first.p, 0xff, (size_t) sizeof(uint32_t) << 24, c->stream_aux));
+    }
+    if (!b.d_raw_in_gen.p) {
+        if (int rc = b.d_raw_in_gen.reserve_exact(c, 2 * ((1u << 24) / 8))) return rc;
+        HIPCHK(c, hipMemsetAsync(b.d_raw_in_gen.p, 0, 2 * ((1u << 24) / 8), c->stream_aux));
+    }
+    if (!b.d_raw_in_crc.p) {
+        if (int rc = b.d_raw_in_crc.reserve_exact(c, 256 * sizeof(uint32_t))) return rc;
+        HIPCHK(c, hipMemcpy(b.d_raw_in_crc.p, crc_tables().byte_table, 256 * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    // the filter's generations into their bitmaps
+    IcaoFilter &flt = c->resolver.filter();
+    const std::vector<uint32_t> &ma = flt.members(true), &mi = flt.members(false);
+    const uint32_t na = (uint32_t) ma.size(), ni = (uint32_t) mi.size();
+    if (int rc = b.d_raw_in_members.reserve(c, ((uint64_t) na + ni + 1) * sizeof(uint32_t))) return rc;
+    uint32_t *d_members = b.d_raw_in_members.as<uint32_t>(), *gen_active = b.d_raw_in_gen.as<uint32_t>(), *gen_inactive = gen_active + (1u << 24) / 32;
+    if (na) HIPCHK(c, hipMemcpyAsync(d_members, ma.data(), na * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream_aux));
+    if (ni) HIPCHK(c, hipMemcpyAsync(d_members + na, mi.data(), ni * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream_aux));
+    launch_raw_in_scatter(d_members, na, gen_active, 1, c->stream_aux);
+    launch_raw_in_scatter(d_members + na, ni, gen_inactive, 1, c->stream_aux);
+    // occupied > buckets / 3 makes the table grow (icao_filter.c:127); between calls occupied <= buckets / 3
+    const uint64_t buckets = 1ull << flt.table_bits(), third = buckets / 3;
+    const uint64_t kstar = flt.table_bits() >= 20 ? 0 : (flt.occupied() <= third ? third - flt.occupied() + 1 : 1);
+
+    const UatScratch w = {b.d_raw_in_meta.as<uint16_t>(), b.d_raw_in_blocks.as<uint32_t>(), b.d_raw_in_off.as<unsigned long long>(), b.d_raw_in_total.as<unsigned long long>(), nb};
+    RawInParams p;
+    p.text = a.text; p.nbytes = a.nbytes; p.now_ms = a.now_ms;
+    p.cfg = RawInConfig{c->cfg.nfix_crc, c->cfg.fixDF, (int32_t) c->cfg.mode_ac};
+    p.tb = RawInTables{b.d_raw_in_crc.as<uint32_t>(), c->d_tab_long, c->d_tab_short, (uint32_t) c->n_long, (uint32_t) c->n_short};
+    p.cand_rec = b.d_raw_in_cand_rec.as<mgpu_msg>(); p.cand_sig = b.d_raw_in_cand_sig.as<double>();
+    p.cand_line = b.d_raw_in_cand_line.as<uint32_t>(); p.cand_meta = b.d_raw_in_cand_meta.as<uint32_t>(); p.cand_cap = cand_cap;
+    p.gen_active = gen_active; p.gen_inactive = gen_inactive; p.first = b.d_raw_in_first.as<uint32_t>();
+    p.new_adds = b.d_raw_in_new_adds.as<uint32_t>(); p.kstar = kstar;
+    p.msgs = a.msgs; p.line_of = (unsigned long long *) a.line_of; p.signal_level = a.signal_level; p.msgs_cap = a.msgs ? a.msgs_cap : 0;
+    p.line_class = a.line_class; p.line_class_cap = a.line_class ? a.line_class_cap : 0; p.line_base = line_base;
+    launch_raw_in_front(p, w, c->stream_aux);
+    HIPCHK(c, hipGetLastError());
+    unsigned long long total[3] = {0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(total, w.total, sizeof total, hipMemcpyDeviceToHost, c->stream_aux));
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    unsigned long long misc[16];
+    memset(misc, 0, sizeof misc);
+    int rc = MGPU_OK;
+    const size_t ncls = p.line_class ? (size_t) std::min<uint64_t>(total[0], p.line_class_cap) : 0;   // "not a frame" is 0: only candidates store a class
+    if (total[2] > cand_cap) { c->err = "raw decode: more candidates than the text can hold"; rc = MGPU_E_OVERFLOW; }   // (cannot happen: raw_in_max_cands)
+    else if (total[2]) {
+        unsigned long long *d_misc = b.d_raw_in_misc.as<unsigned long long>();
+        HIPCHK(c, hipMemsetAsync(d_misc, 0, sizeof misc, c->stream_aux));
+        HIPCHK(c, hipMemsetAsync(d_misc + 8, 0xff, sizeof(unsigned long long), c->stream_aux));
+        if (ncls) HIPCHK(c, hipMemsetAsync(p.line_class, 0, ncls, c->stream_aux));
+        launch_raw_in_resolve(p, (uint32_t) total[2], b.d_raw_in_cb.as<uint32_t>(), b.d_raw_in_co.as<unsigned long long>(), d_misc, c->stream_aux);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(misc, d_misc, sizeof misc, hipMemcpyDeviceToHost, c->stream_aux));
+    } else if (ncls) HIPCHK(c, hipMemsetAsync(p.line_class, 0, ncls, c->stream_aux));
+    launch_raw_in_scatter(d_members, na, gen_active, 0, c->stream_aux);
+    launch_raw_in_scatter(d_members + na, ni, gen_inactive, 0, c->stream_aux);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    if (rc) return rc;
+    n->lines = total[0]; n->consumed = total[1]; n->msgs = misc[10];
+    for (int k = 1; k < 7; ++k) n->cn[k] = misc[k];
+    n->cn[0] = misc[2] + misc[3] + misc[4] + misc[5] + misc[6];   // remote_received_modes: every Mode S line that reached the decode
+    if (misc[9]) {                                              // the new adds, in the reference's order, into the context's filter
+        const size_t at = adds->size();
+        adds->resize(at + misc[9]);
+        HIPCHK(c, hipMemcpy(adds->data() + at, p.new_adds, misc[9] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (size_t k = at; k < adds->size(); ++k) flt.add((*adds)[k]);
+    }
+    return MGPU_OK;
+}
+
+// The generation bitmaps are zero and first[] is all ones OUTSIDE a call: a call that ends early (a HIP error between the scatter-in
+// and the passes that put them back) gives the three tables up, and the next call allocates and initialises them again.
+static int raw_decode_dev(mgpu_ctx *c, const struct mgpu_raw_in_args &a, uint64_t line_base, RawInCounts *n, std::vector<uint32_t> *adds) {
+    const int rc = raw_decode_passes(c, a, line_base, n, adds);
+    if (rc != MGPU_OK) {
+        (void) hipStreamSynchronize(c->stream_aux);
+        c->behind->d_raw_in_first.release();
+        c->behind->d_raw_in_gen.release();
+    }
+    return rc;
+}
+
+static bool raw_in_args_ok(const struct mgpu_raw_in_args *a) {
+    if (!a || a->size < sizeof(struct mgpu_raw_in_args) || !a->consumed || !a->nlines || !a->nmsgs || !a->counters) return false;
+    if (a->nbytes >= (1ull << 32) || a->msgs_cap > UINT64_MAX / sizeof(mgpu_msg)) return false;
+    if (a->now_ms < 0 || a->now_ms >= 253402300800000ll) return false;
+    if (a->nbytes && !a->text) return false;
+    if ((a->msgs_cap && !a->msgs) || (a->line_class_cap && !a->line_class)) return false;
+    return true;
+}
+
+static void raw_in_report(const struct mgpu_raw_in_args *a, const RawInCounts &n) {
+    *a->consumed = n.consumed;
+    *a->nlines = n.lines;
+    *a->nmsgs = n.msgs;
+    struct mgpu_raw_in_counters &k = *a->counters;
+    k.remote_received_modes = n.cn[0]; k.remote_received_modeac = n.cn[1]; k.remote_rejected_unknown_icao = n.cn[2]; k.remote_rejected_bad = n.cn[3];
+    for (int i = 0; i < 3; ++i) k.remote_accepted[i] = n.cn[4 + i];
+}
+
+// the end of a call: on overflow the filter goes back to where it stood; otherwise the pre-screen learns the new addresses, as
+// mgpu_filter_add teaches it one (nothing is in flight behind the drain)
+static int raw_in_finish(mgpu_ctx *c, const struct mgpu_raw_in_args *a, const RawInCounts &n, const IcaoFilter::Snapshot &before, const std::vector<uint32_t> &adds) {
+    if (n.msgs > a->msgs_cap || (a->line_class && n.lines > a->line_class_cap)) {
+        c->resolver.filter().restore(before);
+        c->err = n.msgs > a->msgs_cap ? "raw decode: more messages than the array holds" : "raw decode: more lines than line_class holds";
+        return MGPU_E_OVERFLOW;
+    }
+    if (!adds.empty()) {
+        Behind &b = *c->behind;
+        if (int rc = b.d_raw_in_members.reserve(c, adds.size() * sizeof(uint32_t))) return rc;
+        HIPCHK(c, hipMemcpyAsync(b.d_raw_in_members.p, adds.data(), adds.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream_aux));
+        launch_raw_in_scatter(b.d_raw_in_members.as<uint32_t>(), (uint32_t) adds.size(), c->d_adder_bitmap, 1, c->stream_aux);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    }
+    return MGPU_OK;
+}
+
+int mgpu_raw_decode_device(mgpu_ctx *c, const struct mgpu_raw_in_args *a) {
+    if (!c || !raw_in_args_ok(a)) return MGPU_E_INVAL;
+    if (((uintptr_t) a->msgs | (uintptr_t) a->line_of | (uintptr_t) a->signal_level) & 7u) return MGPU_E_INVAL;
+    RawInCounts n;
+    raw_in_report(a, n);
+    if (a->nbytes == 0) return MGPU_OK;
+    { const int rc = drain(c); if (rc != MGPU_OK) return rc; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    IcaoFilter::Snapshot before;
+    c->resolver.filter().snapshot(before);
+    std::vector<uint32_t> adds;
+    if (int rc = raw_decode_dev(c, *a, 0, &n, &adds)) { c->resolver.filter().restore(before); return rc; }
+    raw_in_report(a, n);
+    return raw_in_finish(c, a, n, before, adds);
+}
+
+int mgpu_raw_decode(mgpu_ctx *c, const struct mgpu_raw_in_args *a) {
+    if (!c || !raw_in_args_ok(a)) return MGPU_E_INVAL;
+    RawInCounts all;
+    raw_in_report(a, all);
+    if (a->nbytes == 0) return MGPU_OK;
+    { const int rc = drain(c); if (rc != MGPU_OK) return rc; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    Behind &b = *c->behind;
+    IcaoFilter::Snapshot before;
+    c->resolver.filter().snapshot(before);
+    std::vector<uint32_t> adds;
+    uint64_t pass = std::min<uint64_t>(a->pass_bytes ? a->pass_bytes : kUatDefaultPass, a->nbytes);
+    for (uint64_t at = 0; at < a->nbytes;) {
+        const uint64_t nb = std::min<uint64_t>(pass, a->nbytes - at);
+        // what this pass may write: what the caller's arrays still hold, and no more than nb bytes of text can give
+        const uint64_t msg_room = a->msgs_cap > all.msgs ? std::min<uint64_t>(a->msgs_cap - all.msgs, raw_in_max_cands(nb)) : 0;
+        const uint64_t cls_room = a->line_class_cap > all.lines ? std::min<uint64_t>(a->line_class_cap - all.lines, nb) : 0;
+        int rc;
+        if ((rc = b.d_raw_in_text.reserve(c, nb + 64)) || (rc = b.d_raw_in_msgs.reserve(c, (msg_room + 1) * sizeof(mgpu_msg))) ||
+            (rc = b.d_raw_in_line_of.reserve(c, (msg_room + 1) * sizeof(uint64_t))) || (rc = b.d_raw_in_sig.reserve(c, (msg_room + 1) * sizeof(double))) ||
+            (rc = b.d_raw_in_cls.reserve(c, cls_room + 1))) { c->resolver.filter().restore(before); return rc; }
+        struct mgpu_raw_in_args d = *a;
+        d.text = b.d_raw_in_text.as<uint8_t>(); d.nbytes = nb;
+        d.msgs = b.d_raw_in_msgs.as<mgpu_msg>(); d.msgs_cap = msg_room;
+        d.line_of = a->line_of ? b.d_raw_in_line_of.as<uint64_t>() : nullptr;
+        d.signal_level = a->signal_level ? b.d_raw_in_sig.as<double>() : nullptr;
+        d.line_class = a->line_class ? b.d_raw_in_cls.as<uint8_t>() : nullptr; d.line_class_cap = cls_room;
+        HIPCHK(c, hipMemcpyAsync(b.d_raw_in_text.p, a->text + at, nb, hipMemcpyHostToDevice, c->stream_aux));
+        RawInCounts n;
+        const size_t adds_before = adds.size();
+        IcaoFilter::Snapshot pass_before;
+        const bool may_repeat = at + nb < a->nbytes;
+        if (may_repeat) c->resolver.filter().snapshot(pass_before);
+        if ((rc = raw_decode_dev(c, d, all.lines, &n, &adds))) { c->resolver.filter().restore(before); return rc; }
+        if (n.consumed == 0 && may_repeat) {                  // a line longer than the pass: a larger pass, from the same filter
+            c->resolver.filter().restore(pass_before);
+            adds.resize(adds_before);
+            pass = pass > a->nbytes / 2 ? a->nbytes : 2 * pass;
+            continue;
+        }
+        // (the pass stored below its rooms only: the copies stay inside the caller's arrays)
+        const uint64_t nmsg = std::min<uint64_t>(n.msgs, msg_room), ncls = std::min<uint64_t>(n.lines, cls_room);
+        if (nmsg) HIPCHK(c, hipMemcpy(a->msgs + all.msgs, d.msgs, nmsg * sizeof(mgpu_msg), hipMemcpyDeviceToHost));
+        if (nmsg && a->line_of) HIPCHK(c, hipMemcpy(a->line_of + all.msgs, d.line_of, nmsg * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (nmsg && a->signal_level) HIPCHK(c, hipMemcpy(a->signal_level + all.msgs, d.signal_level, nmsg * sizeof(double), hipMemcpyDeviceToHost));
+        if (ncls && a->line_class) HIPCHK(c, hipMemcpy(a->line_class + all.lines, d.line_class, ncls, hipMemcpyDeviceToHost));
+        all.lines += n.lines; all.msgs += n.msgs;
+        for (int k = 0; k < 7; ++k) all.cn[k] += n.cn[k];
+        if (n.consumed == 0) break;                           // the rest has no terminator
+        at += n.consumed;
+        all.consumed = at;
+    }
+    raw_in_report(a, all);
+    return raw_in_finish(c, a, all, before, adds);
 }
 
 // ---- ASTERIX input: readAsterix + decodeAsterixMessage over a length-chained stream (asterix_in_format.h, kernels/asterix_in.inc) ----

@@ -48,6 +48,13 @@ struct Behind {
     DevBuf d_uat_meta, d_uat_blocks, d_uat_off, d_uat_total, d_uat_deferred, d_uat_sig_table, d_uat_in, d_uat_out, d_uat_msgs, d_uat_sig, d_uat_line_of;
     // SBS input (kernels/sbs_in.inc): the UAT input's scratch layout in buffers of its own; the host-array form's staged text and its results
     DevBuf d_sbs_in_meta, d_sbs_in_blocks, d_sbs_in_off, d_sbs_in_total, d_sbs_in_deferred, d_sbs_in_text, d_sbs_in_recs, d_sbs_in_line_of;
+    // Raw input (kernels/raw_in.inc): the UAT input's per-tile scratch in buffers of its own; per candidate the record, the signal, the
+    // line, the class word and the new adds; per workgroup of candidates two words and two offsets; the counters, L* and two totals;
+    // the first-adder table (64 MiB, allocated and set to all ones by the first call), the two generation bitmaps (2 MiB each, zero
+    // outside a call) and the members lists scattered into them; the CRC byte table; the host-array form's staged text and results
+    DevBuf d_raw_in_meta, d_raw_in_blocks, d_raw_in_off, d_raw_in_total, d_raw_in_cand_rec, d_raw_in_cand_sig, d_raw_in_cand_line, d_raw_in_cand_meta, d_raw_in_new_adds;
+    DevBuf d_raw_in_cb, d_raw_in_co, d_raw_in_misc, d_raw_in_first, d_raw_in_gen, d_raw_in_members, d_raw_in_crc;
+    DevBuf d_raw_in_text, d_raw_in_msgs, d_raw_in_line_of, d_raw_in_sig, d_raw_in_cls;
     // ASTERIX input (kernels/asterix_in.inc): the tiles' and the groups' exit maps; the entries; three bitmaps per tile; per tile four
     // words and two offsets; the nine totals; the host-array form's staged stream and its results
     DevBuf d_ast_in_maps, d_ast_in_gmaps, d_ast_in_entry, d_ast_in_bits, d_ast_in_blocks, d_ast_in_off, d_ast_in_total, d_ast_in_data, d_ast_in_recs, d_ast_in_frame_of;

@@ -18,6 +18,7 @@
 #include <cstdint>
 
 #include "../../include/modes_gpu.h"   // struct mgpu_msg (the beast encoder reads it on the device)
+#include "raw_in_format.h"
 
 namespace mgpu {
 
@@ -323,6 +324,34 @@ struct SbsInParams {
     uint32_t source;
 };
 void launch_sbs_decode(const SbsInParams &a, const UatScratch &w, hipStream_t s);
+// Raw input (kernels/raw_in.inc; decodeHexMessage + the front of decodeModesMessage over AVR lines, raw_in_format.h): the tiles, the halo
+// and the per-tile scratch of the UAT input (UatScratch's words per lane and per tile count candidates where it says frames), then
+// passes over the candidates that settle the ICAO filter's answers in parallel
+struct RawInParams {
+    const uint8_t *text;              // any alignment
+    uint64_t nbytes;
+    int64_t now_ms;
+    RawInConfig cfg;
+    RawInTables tb;                   // device pointers
+    mgpu_msg *cand_rec;               // per candidate, in line order: the record, the signal, the line, class | correctedbits | adder | address
+    double *cand_sig;
+    uint32_t *cand_line, *cand_meta;
+    uint64_t cand_cap;
+    const uint32_t *gen_active, *gen_inactive;   // 2^24 bits each: the filter's generations at the start of the call
+    uint32_t *first;                  // 2^24 words, all ones outside a call: the first adder candidate of an address
+    uint32_t *new_adds;               // cand_cap words: the addresses that enter the active generation, in line order
+    uint64_t kstar;                   // the new add that makes the table grow (1-based); 0: none can
+    mgpu_msg *msgs;                   // nothing at or beyond msgs + msgs_cap is stored
+    unsigned long long *line_of;      // optional
+    double *signal_level;             // optional
+    uint64_t msgs_cap;
+    uint8_t *line_class;              // optional: nothing at or beyond line_class + line_class_cap is stored
+    uint64_t line_class_cap;
+    uint64_t line_base;               // added to every line_of (the host form's passes)
+};
+void launch_raw_in_scatter(const uint32_t *members, uint32_t n, uint32_t *bitmap, int set, hipStream_t s);
+void launch_raw_in_front(const RawInParams &a, const UatScratch &w, hipStream_t s);
+void launch_raw_in_resolve(const RawInParams &a, uint32_t ncand, uint32_t *cb, unsigned long long *co, unsigned long long *misc, hipStream_t s);
 // ASTERIX input (kernels/asterix_in.inc; readAsterix + decodeAsterixMessage over a length-chained stream, asterix_in_format.h)
 constexpr uint32_t kAstTile = 65536;          // bytes per tile: a length is below 65536, so a chain that enters tile t leaves it into tile t + 1
 constexpr uint32_t kAstGroup = 32;            // tiles whose exit maps are composed into one

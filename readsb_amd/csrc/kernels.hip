@@ -16,6 +16,8 @@
 //   k_snip_*         `--snip`: quiet stretches of a UC8 capture cut down to their first 32 samples (readsb.c:1187-1206)
 //   k_uat_*          `--net-uat-in-port`: dump978 downlink lines to DF18 extended squitters (uat2esnt/uat2esnt.c, uat_decode.c)
 //   k_sbs_in_*       `--net-sbs-in-port` and the MLAT / JAERO / PRIO ports: BaseStation lines to aircraft records (net_io.c:2952-3178)
+//   k_raw_in_*       `--net-ri-port`: AVR raw lines to accepted messages, the ICAO filter's answers resolved in parallel (net_io.c:4104-4317,
+//                    mode_s.c:443-606, 766-779)
 //   k_ast_in_*       `--net-asterix-in-port`: a length-chained stream of CAT021 records to aircraft records (net_io.c:4643-4659, 1922-2407)
 //
 // No MFMA anywhere: this is HBM-bound integer/byte streaming work.  All arithmetic on the
@@ -138,6 +140,7 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 #include "kernels/snip.inc"
 #include "kernels/uat.inc"
 #include "kernels/sbs_in.inc"
+#include "kernels/raw_in.inc"
 #include "kernels/asterix_in.inc"
 #include "kernels/fields.inc"
 #include "kernels/gate.inc"

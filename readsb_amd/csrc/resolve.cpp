@@ -15,103 +15,6 @@ static constexpr uint32_t kShowOnlyDefault = 0xff123456u;   // BADDR, readsb.h:2
 static constexpr int64_t kFilterTtlMs = 60000;              // MODES_ICAO_FILTER_TTL, readsb.h:315
 static constexpr int64_t kBufferSpanMs = 64;                // > the clock span of one 131072-sample buffer (54.7 ms) + one frame
 
-IcaoFilter::IcaoFilter() {
-    for (int g = 0; g < 2; ++g) bits_[g].assign(1u << 18, 0);
-    init();
-}
-
-void IcaoFilter::clear_gen(int g) {
-    if (drops_)   // what leaves the union: members of this generation the other one does not hold
-        for (uint32_t a : members_[g])
-            if (!((bits_[g ^ 1][a >> 6] >> (a & 63)) & 1)) drops_->push_back(a);
-    for (uint32_t a : members_[g]) bits_[g][a >> 6] = 0;
-    members_[g].clear();
-    big_[g].clear();
-}
-
-void IcaoFilter::init() {
-    clear_gen(0);
-    clear_gen(1);
-    active_ = 0;
-    occupied_ = 0;
-    filter_bits_ = 8;
-}
-
-bool IcaoFilter::big_test(uint32_t addr) const {
-    for (int g = 0; g < 2; ++g)
-        if (std::find(big_[g].begin(), big_[g].end(), addr) != big_[g].end()) return true;
-    return false;
-}
-
-void IcaoFilter::resize(uint32_t bits) {
-    // two fresh tables; only the ACTIVE generation's entries are re-inserted
-    filter_bits_ = bits;
-    clear_gen(active_ ^ 1);
-    occupied_ = (uint32_t) (members_[active_].size() + big_[active_].size());
-}
-
-void IcaoFilter::add(uint32_t addr) {
-    bool inserted = false;
-    if (addr < (1u << 24)) {
-        uint64_t &w = bits_[active_][addr >> 6];
-        const uint64_t bit = 1ull << (addr & 63);
-        if (!(w & bit)) {
-            w |= bit; members_[active_].push_back(addr); inserted = true;
-            if (news_ && !((bits_[active_ ^ 1][addr >> 6] >> (addr & 63)) & 1)) news_->push_back(addr);
-        }
-    } else if (std::find(big_[active_].begin(), big_[active_].end(), addr) == big_[active_].end()) {
-        big_[active_].push_back(addr);
-        inserted = true;
-    }
-    if (inserted) ++occupied_;
-    if (occupied_ > (1u << filter_bits_) / 3 && filter_bits_ < 20) resize(filter_bits_ + 1);
-}
-
-void IcaoFilter::expire() {
-    if (occupied_ < (1u << filter_bits_) / 9 && filter_bits_ > 8) resize(filter_bits_ - 1);
-    occupied_ = 0;
-    clear_gen(active_ ^ 1);
-    active_ ^= 1;
-}
-
-void IcaoFilter::snapshot(Snapshot &s) const {
-    for (int g = 0; g < 2; ++g) { s.members[g] = members_[g]; s.big[g] = big_[g]; }
-    s.active = active_; s.occupied = occupied_; s.filter_bits = filter_bits_;
-}
-
-void IcaoFilter::restore(const Snapshot &s) {
-    std::vector<uint32_t> *keep = drops_;
-    drops_ = nullptr;   // (news_ is only touched by add)
-    for (int g = 0; g < 2; ++g) {
-        clear_gen(g);
-        for (uint32_t a : s.members[g]) bits_[g][a >> 6] |= 1ull << (a & 63);
-        members_[g] = s.members[g];
-        big_[g] = s.big[g];
-    }
-    active_ = s.active; occupied_ = s.occupied; filter_bits_ = s.filter_bits;
-    drops_ = keep;
-}
-
-void IcaoFilter::union_sorted(std::vector<uint32_t> &out) const {
-    out.clear();
-    out.insert(out.end(), members_[0].begin(), members_[0].end());
-    out.insert(out.end(), members_[1].begin(), members_[1].end());
-    std::sort(out.begin(), out.end());
-    out.erase(std::unique(out.begin(), out.end()), out.end());
-}
-
-bool IcaoFilter::same_as(const IcaoFilter &o) const {
-    if (occupied_ != o.occupied_ || filter_bits_ != o.filter_bits_) return false;
-    for (int g = 0; g < 2; ++g) {
-        std::vector<uint32_t> x = members_[g ? active_ ^ 1 : active_], y = o.members_[g ? o.active_ ^ 1 : o.active_];
-        std::vector<uint32_t> bx = big_[g ? active_ ^ 1 : active_], by = o.big_[g ? o.active_ ^ 1 : o.active_];
-        std::sort(x.begin(), x.end()); std::sort(y.begin(), y.end());
-        std::sort(bx.begin(), bx.end()); std::sort(by.begin(), by.end());
-        if (x != y || bx != by) return false;
-    }
-    return true;
-}
-
 bool Resolver::apply_device_walk(const uint32_t *per_buf, const uint32_t *adds, uint32_t nbuf, int32_t flip) {
     IcaoFilter::Snapshot snap;
     filter_.snapshot(snap);

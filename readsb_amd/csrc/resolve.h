@@ -14,54 +14,10 @@
 #include <vector>
 
 #include "../../include/modes_gpu.h"
+#include "icao_filter.h"
 #include "kernels.h"
 
 namespace mgpu {
-
-// Exact model of icao_filter.c: two generations, `occupied`, table size.  Bucket placement never
-// shows in results; membership, the occupied count and the grow/shrink thresholds do, because
-// growing re-inserts only the active generation (icaoFilterResize, icao_filter.c:65-93).
-class IcaoFilter {
-  public:
-    IcaoFilter();
-    void init();                       // icaoFilterInit (:47-59)
-    void add(uint32_t addr);           // icaoFilterAdd (:112-130)
-    bool test(uint32_t addr) const {   // icaoFilterTest (:132-154)
-        return addr < (1u << 24) ? (((bits_[0][addr >> 6] | bits_[1][addr >> 6]) >> (addr & 63)) & 1) : big_test(addr);
-    }
-    void expire();                     // icaoFilterExpire (:96-110)
-    uint32_t occupied() const { return occupied_; }
-    uint32_t table_bits() const { return filter_bits_; }
-
-    // --- support for the speculative parallel walk (resolve.cpp: Resolver::spec_walk / commit_segment) ---
-    struct Snapshot {
-        std::vector<uint32_t> members[2], big[2];
-        int active = 0;
-        uint32_t occupied = 0, filter_bits = 8;
-    };
-    void snapshot(Snapshot &s) const;
-    void restore(const Snapshot &s);
-    int active_index() const { return active_; }
-    void union_sorted(std::vector<uint32_t> &out) const;      // addresses < 2^24 in either generation, ascending
-    const std::vector<uint32_t> &members(bool active) const { return members_[active ? active_ : active_ ^ 1]; }   // addresses < 2^24
-    bool same_as(const IcaoFilter &o) const;                  // membership per generation, occupied, table size
-    bool in_generation(uint32_t addr, bool active) const {    // addr < 2^24
-        return (bits_[active ? active_ : active_ ^ 1][addr >> 6] >> (addr & 63)) & 1;
-    }
-    // addresses that leave the union (expire / resize) and addresses that enter it (first add)
-    void track_changes(std::vector<uint32_t> *drops, std::vector<uint32_t> *news) { drops_ = drops; news_ = news; }
-
-  private:
-    void resize(uint32_t bits);
-    bool big_test(uint32_t addr) const;
-    void clear_gen(int g);
-    std::vector<uint64_t> bits_[2];       // 2^24-bit membership bitmap per generation
-    std::vector<uint32_t> members_[2];    // for O(members) clearing
-    std::vector<uint32_t> big_[2];        // addresses >= 2^24 (only Modes.show_only's default)
-    int active_ = 0;
-    uint32_t occupied_ = 0, filter_bits_ = 8;
-    std::vector<uint32_t> *drops_ = nullptr, *news_ = nullptr;
-};
 
 struct BufferClock {
     int64_t sampleTimestamp;   // mag_buf.sampleTimestamp (12 MHz ticks)
