@@ -1456,6 +1456,130 @@ int mgpu_raw_decode_device(mgpu_ctx *ctx, const struct mgpu_raw_in_args *args); 
  * frame (*out zeroed), or MGPU_E_INVAL.  Needs no context and no GPU. */
 int mgpu_raw_parse_line_host(const uint8_t *line, uint64_t len, int64_t now_ms, const struct mgpu_raw_in_config *cfg, struct mgpu_raw_in_line *out);
 
+/* ---- Beast input: a binary stream to accepted message records (`--net-bi-port`, the beast_in connectors, sdr_beast.c; readBeast,
+ * net_io.c:4737-5018, with decodeBinMessage, :3804-3961, as its read handler; kernels/beast_in.inc, beast_in_format.h) ------------
+ * One call is one readBeast over [data, data + nbytes) with remote = 1 and now = now_ms: the stream mgpu_beast_encode_ex* and
+ * readsb_gpu_gather --merge write, read back to the struct mgpu_msg records the demodulator and the raw input give, each with the
+ * receiver id in force at its frame.  The byte at data[nbytes] counts as 0 (the reference NUL-terminates its client buffer, :5182);
+ * nothing at or beyond nbytes is read.
+ *   Modelled, quirk for quirk:
+ *     garbage up to the next 0x1a, counted in remote_malformed_beast when a 0x1a is found behind it (:4746-4752);
+ *     the 0xe3 receiver-id prefix with its own escape loop and eom bookkeeping (:4819-4857): an id byte 0x1a followed by another byte
+ *       abandons the prefix with the scan resuming BEHIND that 0x1a; `eom + 2 > eod` is incomplete; with cfg.net_ingest the id is
+ *       not taken; behind the id the same iteration goes on only at a 0x1a, and 0xe3 / 0xe8 there are unknown types.
+ *       c->receiverId enters as receiver_id_in and leaves as *receiver_id_out;
+ *     the type bytes: '1' '2' '3' (2, 7, 14 bytes behind type, six timestamp bytes and a signal byte), '5' (eom = p + 22), 'P' (eom
+ *       = p + 4), 'W' (som += 2, counted in ncommands; the ping it may send is not modelled), anything else som += 2 and two bytes
+ *       of garbage;
+ *     body un-escaping (:4936-4971): `1a 1a` is one byte and extends eom; `1a` and another byte abandons the frame, everything up to
+ *       that 0x1a is garbage and scanning resumes at it;
+ *     every "incomplete, retry later" break: *consumed is the frame's 0x1a (behind a taken prefix the inner one; the id stays taken);
+ *     the tail rule (:5010-5015): more than 256 unconsumed bytes at the end are all garbage and are consumed;
+ *     decodeBinMessage for '1' '2' '3': timestamp the six bytes big endian, signalLevel = (b / 255.0)^2 in two double operations,
+ *       sysTimestamp = now_ms; Mode A/C with cfg.mode_ac off is counted in remote_received_modeac and dropped (:3825-3831; the raw
+ *       input does not count it); then decodeModeAMessage, or the decode and the filter question of the raw input (above), the
+ *       filter moved on and the pre-screen taught as there.  A record is what mgpu_raw_decode leaves: raw the bytes as received,
+ *       sig_sumsq = (257 b)^2, sig_len 1.  '5' and 'P' frames are framed, classed and located, nothing else.
+ *   Stops, as the ASTERIX input reports its stops: *consumed = *stop_off = the stopping frame's 0x1a, *stop says which:
+ *     MGPU_BEAST_STOP_SYNTH  0xe8, a synthetic timestamp (all eight bytes there): the reference disconnects without
+ *                            --devel=accept_synthetic;
+ *     MGPU_BEAST_STOP_UUID   0xe4: read_uuid depends on receiverIdLocked and can step beyond the buffer; once per connection, so the
+ *                            host handles it and calls again.  (Behind a taken 0xe3 prefix the id is taken and the stop is the inner 0x1a.)
+ *     Only the first stop on the chain from offset 0 counts; the same bytes in a payload or in garbage stop nothing.
+ *     MGPU_BEAST_STOP_END otherwise, *stop_off = *consumed.
+ *   Not modelled: Modes.receiver_focus, incrementId, ping and rtt rejection, unreasonable_messagerate and receiverCheckBad; the
+ *     c->garbage disconnect bookkeeping; handle_radarcape_position and pongReceived; the 'H' type (never framed by readBeast);
+ *     netUseMessage and beyond.
+ *   Per message, in stream order: msgs, receiver_id (the array mgpu_beast_encode_ex takes as ids), signal_level (optional),
+ *     frame_of (optional: the handler call that gave it).  Per handler call (optional, frames_cap entries): frame_class
+ *     (MGPU_BEAST_IN_*) and frame_off (the offset of the frame's 0x1a).
+ *   Bounds: a handler call needs 5 bytes, so *nframes <= nbytes / 5 + 1; a message needs 11, so *nmsgs <= nbytes / 11 + 1.
+ *   args->size smaller than sizeof(struct mgpu_beast_in_args), a NULL ctx, args, consumed, nframes, nmsgs, stop, stop_off,
+ *     receiver_id_out or counters, data NULL with nbytes != 0, msgs or receiver_id NULL with msgs_cap != 0, frame_class and frame_off
+ *     both NULL with frames_cap != 0, nbytes >= 2^32, now_ms outside [0, 253402300800000): MGPU_E_INVAL.  nbytes == 0: MGPU_OK
+ *     with zeros (and *receiver_id_out = receiver_id_in).  More messages than msgs_cap, or (with frame_class or frame_off) more
+ *     handler calls than frames_cap: MGPU_E_OVERFLOW with *nmsgs and *nframes = what is needed; nothing is stored at or beyond a
+ *     capacity and the filter goes back to where it stood before the call.  The calls drain the pipeline first.
+ *   mgpu_beast_decode: every array in host memory; the stream is staged in passes of pass_bytes (0: the library's default), each cut
+ *     at the last som it reached, the remainder, the receiver id and the filter carried, the tail rule applied at the real end only:
+ *     exactly the result of one call over the whole stream.
+ *   mgpu_beast_decode_device: data, msgs, receiver_id, signal_level, frame_of, frame_class, frame_off device pointers (data at any
+ *     alignment; the 8-byte arrays 8-byte aligned); the counts are in host memory.  pass_bytes is ignored. */
+#define MGPU_BEAST_IN_MODEAC     1u   /* a Mode A/C record (accepted); the values up to _UNKNOWN are MGPU_RAW_*'s */
+#define MGPU_BEAST_IN_BAD        2u   /* rejected bad */
+#define MGPU_BEAST_IN_ACCEPT     3u   /* accepted */
+#define MGPU_BEAST_IN_COND       4u   /* mgpu_beast_parse_host only: accepted iff addr is in the filter */
+#define MGPU_BEAST_IN_UNKNOWN    5u   /* rejected unknown ICAO */
+#define MGPU_BEAST_IN_MODEAC_OFF 6u   /* '1' with cfg.mode_ac off: counted, no record */
+#define MGPU_BEAST_IN_POSITION   7u   /* '5' */
+#define MGPU_BEAST_IN_PONG       8u   /* 'P' */
+#define MGPU_BEAST_STOP_END      0u
+#define MGPU_BEAST_STOP_SYNTH    1u
+#define MGPU_BEAST_STOP_UUID     2u
+/* what mgpu_beast_parse_host says of the step at an offset */
+#define MGPU_BEAST_STEP_GARBAGE    0u   /* the byte is no 0x1a: one byte of garbage if a 0x1a follows on the chain */
+#define MGPU_BEAST_STEP_SKIP       1u   /* an abandoned frame or prefix, a prefix without a frame, 'W', an unknown type */
+#define MGPU_BEAST_STEP_FRAME      2u   /* a handler call */
+#define MGPU_BEAST_STEP_INCOMPLETE 3u   /* "retry later": next = the som the loop is left with */
+#define MGPU_BEAST_STEP_SYNTH      4u
+#define MGPU_BEAST_STEP_UUID       5u
+struct mgpu_beast_in_counters {
+    uint64_t remote_received_modes, remote_received_modeac, remote_rejected_unknown_icao, remote_rejected_bad, remote_accepted[3];
+    uint64_t remote_malformed_beast;   /* bytes */
+    uint64_t nreceiver_ids;            /* 0xe3 prefixes taken */
+    uint64_t ncommands;                /* 'W' commands */
+};
+struct mgpu_beast_in_config {
+    uint32_t size;                     /* sizeof(struct mgpu_beast_in_config) */
+    int32_t nfix_crc, fixDF;           /* as in struct mgpu_config */
+    uint32_t mode_ac, net_ingest;
+    uint32_t reserved;                 /* 0 */
+};
+struct mgpu_beast_in_frame {           /* 128 bytes */
+    struct mgpu_msg msg;               /* zero unless cls is MGPU_BEAST_IN_MODEAC, _ACCEPT or _COND */
+    double signal_level;
+    uint64_t next;                     /* the successor offset (step INCOMPLETE, SYNTH, UUID: the som the loop is left with) */
+    uint64_t frame_off;                /* step FRAME: the frame's 0x1a */
+    uint64_t receiver_id;              /* id_set: the id the step leaves in force */
+    uint32_t step;                     /* MGPU_BEAST_STEP_* */
+    uint32_t cls;                      /* step FRAME: MGPU_BEAST_IN_* (never _UNKNOWN); 0 otherwise */
+    uint32_t addr;                     /* the address the filter is asked about (_COND) or learns (adder) */
+    uint32_t adder;                    /* 1: a clean DF17 or a clean DF11 with IID 0 — icaoFilterAdd(addr) */
+    uint32_t garbage;                  /* bytes of remote_malformed_beast the step adds */
+    uint32_t id_set;                   /* 1: a 0xe3 prefix taken */
+    uint32_t command;                  /* 1: a 'W' command */
+    uint32_t reserved;                 /* 0 */
+};
+struct mgpu_beast_in_args {
+    uint32_t size, reserved;           /* sizeof(struct mgpu_beast_in_args), 0 */
+    const uint8_t *data;
+    uint64_t nbytes;
+    int64_t now_ms;
+    uint64_t receiver_id_in;           /* c->receiverId before the call */
+    uint32_t net_ingest, reserved2;    /* Modes.netIngest; 0 */
+    struct mgpu_msg *msgs;             /* msgs_cap entries: the accepted messages in stream order */
+    uint64_t *receiver_id;             /* msgs_cap entries: the id in force at each message's frame */
+    double *signal_level;              /* optional, msgs_cap entries: mm->signalLevel */
+    uint64_t *frame_of;                /* optional, msgs_cap entries: the handler call per message */
+    uint64_t msgs_cap;
+    uint8_t *frame_class;              /* optional, frames_cap entries: MGPU_BEAST_IN_* per handler call */
+    uint64_t *frame_off;               /* optional, frames_cap entries: the offset of each handler call's 0x1a */
+    uint64_t frames_cap;
+    uint64_t *consumed, *nframes, *nmsgs;   /* host, out */
+    uint32_t *stop;                    /* host, out: MGPU_BEAST_STOP_* */
+    uint64_t *stop_off;                /* host, out */
+    uint64_t *receiver_id_out;         /* host, out: c->receiverId after the call */
+    struct mgpu_beast_in_counters *counters;   /* host, out */
+    uint64_t pass_bytes;               /* host form: bytes staged per pass; 0 = the library's default */
+};
+int mgpu_beast_decode(mgpu_ctx *ctx, const struct mgpu_beast_in_args *args);          /* every array in host memory */
+int mgpu_beast_decode_device(mgpu_ctx *ctx, const struct mgpu_beast_in_args *args);   /* data and the per-message / per-call arrays device pointers */
+/* The step of readBeast's loop at `offset` of a host buffer, by the same framer and parser (the CRC tables of cfg->nfix_crc built
+ * once per value): the successor, the kind, and for a handler call its class, record, signal, the address asked about and the adder
+ * flag (MGPU_RAW_COND style).  Returns 1 for a handler call, 0 for any other step, or MGPU_E_INVAL (a NULL argument, offset >=
+ * nbytes).  Needs no context and no GPU. */
+int mgpu_beast_parse_host(const uint8_t *data, uint64_t nbytes, uint64_t offset, int64_t now_ms, const struct mgpu_beast_in_config *cfg, struct mgpu_beast_in_frame *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -250,6 +250,37 @@ class RawInLine(C.Structure):                                         # struct m
     _fields_ = [("msg", C.c_uint8 * 64), ("signal_level", C.c_double), ("cls", C.c_uint32), ("addr", C.c_uint32), ("adder", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class BeastInCounters(C.Structure):                                   # struct mgpu_beast_in_counters
+    _fields_ = [("remote_received_modes", C.c_uint64), ("remote_received_modeac", C.c_uint64), ("remote_rejected_unknown_icao", C.c_uint64),
+                ("remote_rejected_bad", C.c_uint64), ("remote_accepted", C.c_uint64 * 3), ("remote_malformed_beast", C.c_uint64),
+                ("nreceiver_ids", C.c_uint64), ("ncommands", C.c_uint64)]
+
+
+class BeastInConfig(C.Structure):                                     # struct mgpu_beast_in_config
+    _fields_ = [("size", C.c_uint32), ("nfix_crc", C.c_int32), ("fixDF", C.c_int32), ("mode_ac", C.c_uint32), ("net_ingest", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BeastInFrame(C.Structure):                                      # struct mgpu_beast_in_frame: 128 bytes
+    _fields_ = [("msg", C.c_uint8 * 64), ("signal_level", C.c_double), ("next", C.c_uint64), ("frame_off", C.c_uint64), ("receiver_id", C.c_uint64),
+                ("step", C.c_uint32), ("cls", C.c_uint32), ("addr", C.c_uint32), ("adder", C.c_uint32), ("garbage", C.c_uint32), ("id_set", C.c_uint32),
+                ("command", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BeastInArgs(C.Structure):                                       # struct mgpu_beast_in_args
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_uint32), ("data", C.c_void_p), ("nbytes", C.c_uint64), ("now_ms", C.c_int64), ("receiver_id_in", C.c_uint64),
+                ("net_ingest", C.c_uint32), ("reserved2", C.c_uint32), ("msgs", C.c_void_p), ("receiver_id", C.c_void_p), ("signal_level", C.c_void_p),
+                ("frame_of", C.c_void_p), ("msgs_cap", C.c_uint64), ("frame_class", C.c_void_p), ("frame_off", C.c_void_p), ("frames_cap", C.c_uint64),
+                ("consumed", C.POINTER(C.c_uint64)), ("nframes", C.POINTER(C.c_uint64)), ("nmsgs", C.POINTER(C.c_uint64)), ("stop", C.POINTER(C.c_uint32)),
+                ("stop_off", C.POINTER(C.c_uint64)), ("receiver_id_out", C.POINTER(C.c_uint64)), ("counters", C.POINTER(BeastInCounters)), ("pass_bytes", C.c_uint64)]
+
+
+def beast_in_counters_dict(cn):
+    return dict(remote_received_modes=int(cn.remote_received_modes), remote_received_modeac=int(cn.remote_received_modeac),
+                remote_rejected_unknown_icao=int(cn.remote_rejected_unknown_icao), remote_rejected_bad=int(cn.remote_rejected_bad),
+                remote_accepted=[int(x) for x in cn.remote_accepted], remote_malformed_beast=int(cn.remote_malformed_beast),
+                nreceiver_ids=int(cn.nreceiver_ids), ncommands=int(cn.ncommands))
+
+
 class RawInFilter(C.Structure):                                       # struct mgpu_raw_in_filter
     _fields_ = [("gen_active", C.c_void_p), ("gen_inactive", C.c_void_p), ("n_active", C.c_uint64), ("n_inactive", C.c_uint64), ("occupied", C.c_uint32),
                 ("table_bits", C.c_uint32)]
@@ -473,6 +504,10 @@ def load_library():
     lib.mgpu_raw_decode_device.argtypes = [vp, C.POINTER(RawInArgs)]
     lib.mgpu_raw_parse_line_host.argtypes = [vp, u64, C.c_int64, C.POINTER(RawInConfig), C.POINTER(RawInLine)]
     lib.mgpu_raw_decode_host.argtypes = [C.POINTER(RawInArgs), C.POINTER(RawInConfig), C.POINTER(RawInFilter)]
+    lib.mgpu_beast_decode.argtypes = [vp, C.POINTER(BeastInArgs)]
+    lib.mgpu_beast_decode_device.argtypes = [vp, C.POINTER(BeastInArgs)]
+    lib.mgpu_beast_parse_host.argtypes = [vp, u64, u64, C.c_int64, C.POINTER(BeastInConfig), C.POINTER(BeastInFrame)]
+    lib.mgpu_beast_decode_host.argtypes = [C.POINTER(BeastInArgs), C.POINTER(RawInConfig), C.POINTER(RawInFilter)]
     lib.mgpu_asterix_decode.argtypes = [vp, C.POINTER(AsterixInArgs)]
     lib.mgpu_asterix_decode_device.argtypes = [vp, C.POINTER(AsterixInArgs)]
     lib.mgpu_asterix_parse_host.argtypes = [C.POINTER(AsterixInArgs), u64, vp]
@@ -1144,6 +1179,28 @@ class Demodulator:
                         remote_accepted=[int(x) for x in cn.remote_accepted])
         return dict(msgs=msgs[:n].copy(), line_of=line_of[:n].copy(), signal_level=signal[:n].copy(), line_class=cls[:nlines].copy(), consumed=consumed, nlines=nlines,
                     counters=counters)
+
+    def beast_decode(self, data, now_ms=0, receiver_id=0, net_ingest=False, pass_bytes=0):
+        """mgpu_beast_decode on a host byte string of beast binary (`--net-bi-port`): one readBeast with decodeBinMessage behind it —
+        the accepted messages in stream order, each with the receiver id in force at its frame, the ICAO filter's answers as they
+        stand at every frame; the context's filter learns the stream's clean DF17 / DF11 addresses.
+        -> dict(msgs, receiver_id, signal_level, frame_of, frame_class, frame_off, consumed, nframes, stop, stop_off, receiver_id_out, counters)."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        most, mostf = buf.size // 11 + 1, buf.size // 5 + 1   # a message needs 11 bytes, a handler call 5 (beast_in_format.h)
+        msgs, ids = np.zeros(most, dtype=MSG_DTYPE), np.zeros(most, dtype=np.uint64)
+        signal, frame_of = np.empty(most, dtype=np.float64), np.empty(most, dtype=np.uint64)
+        cls, off = np.zeros(mostf, dtype=np.uint8), np.zeros(mostf, dtype=np.uint64)
+        c = [C.c_uint64(0) for _ in range(5)]
+        stop = C.c_uint32(0)
+        cn = BeastInCounters()
+        a = BeastInArgs(C.sizeof(BeastInArgs), 0, buf.ctypes.data if buf.size else None, buf.size, int(now_ms), int(receiver_id), int(bool(net_ingest)), 0,
+                        msgs.ctypes.data, ids.ctypes.data, signal.ctypes.data, frame_of.ctypes.data, most, cls.ctypes.data, off.ctypes.data, mostf,
+                        C.pointer(c[0]), C.pointer(c[1]), C.pointer(c[2]), C.pointer(stop), C.pointer(c[3]), C.pointer(c[4]), C.pointer(cn), int(pass_bytes))
+        self._chk(self.lib.mgpu_beast_decode(self.ctx, C.byref(a)), "mgpu_beast_decode")
+        consumed, nframes, n, stop_off, id_out = (int(x.value) for x in c)
+        return dict(msgs=msgs[:n].copy(), receiver_id=ids[:n].copy(), signal_level=signal[:n].copy(), frame_of=frame_of[:n].copy(), frame_class=cls[:nframes].copy(),
+                    frame_off=off[:nframes].copy(), consumed=consumed, nframes=nframes, stop=int(stop.value), stop_off=stop_off, receiver_id_out=id_out,
+                    counters=beast_in_counters_dict(cn))
 
     def asterix_decode(self, data, source=1, now_ms=0, pass_bytes=0):
         """mgpu_asterix_decode on a host byte string of ASTERIX records (`--net-asterix-in-port`): one record per category-21 frame

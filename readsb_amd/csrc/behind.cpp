@@ -8,6 +8,7 @@
 #include "uat_format.h"
 #include "sbs_in_format.h"
 #include "raw_in_format.h"
+#include "beast_in_host.h"
 #include "asterix_in_format.h"
 
 extern "C" {
@@ -978,17 +979,15 @@ struct RawInCounts {
     uint64_t cn[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
-// a: text, msgs, line_of, signal_level, line_class device pointers, the capacities what this text may store (line_class indexed by
-// this text's own lines).  The counts of this text; the context's filter moved on by the text's new adds, which are appended to
-// *adds (the caller publishes them to the pre-screen's bitmap, or puts the filter back).
-static int raw_decode_passes(mgpu_ctx *c, const struct mgpu_raw_in_args &a, uint64_t line_base, RawInCounts *n, std::vector<uint32_t> *adds) {
+// The filter passes' side of a call (launch_raw_in_resolve), shared with the beast input: the candidate arrays and the tables reserved,
+// the filter's generations scattered into their bitmaps, p's candidate, table and filter fields set.
+struct RawInResolve {
+    uint32_t *d_members, *gen_active, *gen_inactive;
+    uint32_t na, ni;
+};
+static int raw_in_resolve_begin(mgpu_ctx *c, uint64_t cand_cap, RawInParams &p, RawInResolve &r) {
     Behind &b = *c->behind;
-    const size_t nb = (size_t) (a.nbytes / kUatTile + 2);
-    const uint64_t cand_cap = raw_in_max_cands(a.nbytes), ncb = cand_cap / kBlock + 1;
-    if (int rc = b.d_raw_in_meta.reserve(c, nb * kBlock * sizeof(uint16_t))) return rc;
-    if (int rc = b.d_raw_in_blocks.reserve(c, 5 * nb * sizeof(uint32_t))) return rc;
-    if (int rc = b.d_raw_in_off.reserve(c, 3 * nb * sizeof(unsigned long long))) return rc;
-    if (int rc = b.d_raw_in_total.reserve_exact(c, 8 * sizeof(unsigned long long))) return rc;
+    const uint64_t ncb = cand_cap / kBlock + 1;
     if (int rc = b.d_raw_in_cand_rec.reserve(c, cand_cap * sizeof(mgpu_msg))) return rc;
     if (int rc = b.d_raw_in_cand_sig.reserve(c, cand_cap * sizeof(double))) return rc;
     if (int rc = b.d_raw_in_cand_line.reserve(c, cand_cap * sizeof(uint32_t))) return rc;
@@ -1012,26 +1011,70 @@ static int raw_decode_passes(mgpu_ctx *c, const struct mgpu_raw_in_args &a, uint
     // the filter's generations into their bitmaps
     IcaoFilter &flt = c->resolver.filter();
     const std::vector<uint32_t> &ma = flt.members(true), &mi = flt.members(false);
-    const uint32_t na = (uint32_t) ma.size(), ni = (uint32_t) mi.size();
-    if (int rc = b.d_raw_in_members.reserve(c, ((uint64_t) na + ni + 1) * sizeof(uint32_t))) return rc;
-    uint32_t *d_members = b.d_raw_in_members.as<uint32_t>(), *gen_active = b.d_raw_in_gen.as<uint32_t>(), *gen_inactive = gen_active + (1u << 24) / 32;
-    if (na) HIPCHK(c, hipMemcpyAsync(d_members, ma.data(), na * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream_aux));
-    if (ni) HIPCHK(c, hipMemcpyAsync(d_members + na, mi.data(), ni * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream_aux));
-    launch_raw_in_scatter(d_members, na, gen_active, 1, c->stream_aux);
-    launch_raw_in_scatter(d_members + na, ni, gen_inactive, 1, c->stream_aux);
+    r.na = (uint32_t) ma.size(); r.ni = (uint32_t) mi.size();
+    if (int rc = b.d_raw_in_members.reserve(c, ((uint64_t) r.na + r.ni + 1) * sizeof(uint32_t))) return rc;
+    r.d_members = b.d_raw_in_members.as<uint32_t>(); r.gen_active = b.d_raw_in_gen.as<uint32_t>(); r.gen_inactive = r.gen_active + (1u << 24) / 32;
+    if (r.na) HIPCHK(c, hipMemcpyAsync(r.d_members, ma.data(), r.na * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream_aux));
+    if (r.ni) HIPCHK(c, hipMemcpyAsync(r.d_members + r.na, mi.data(), r.ni * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream_aux));
+    launch_raw_in_scatter(r.d_members, r.na, r.gen_active, 1, c->stream_aux);
+    launch_raw_in_scatter(r.d_members + r.na, r.ni, r.gen_inactive, 1, c->stream_aux);
     // occupied > buckets / 3 makes the table grow (icao_filter.c:127); between calls occupied <= buckets / 3
     const uint64_t buckets = 1ull << flt.table_bits(), third = buckets / 3;
     const uint64_t kstar = flt.table_bits() >= 20 ? 0 : (flt.occupied() <= third ? third - flt.occupied() + 1 : 1);
-
-    const UatScratch w = {b.d_raw_in_meta.as<uint16_t>(), b.d_raw_in_blocks.as<uint32_t>(), b.d_raw_in_off.as<unsigned long long>(), b.d_raw_in_total.as<unsigned long long>(), nb};
-    RawInParams p;
-    p.text = a.text; p.nbytes = a.nbytes; p.now_ms = a.now_ms;
     p.cfg = RawInConfig{c->cfg.nfix_crc, c->cfg.fixDF, (int32_t) c->cfg.mode_ac};
     p.tb = RawInTables{b.d_raw_in_crc.as<uint32_t>(), c->d_tab_long, c->d_tab_short, (uint32_t) c->n_long, (uint32_t) c->n_short};
     p.cand_rec = b.d_raw_in_cand_rec.as<mgpu_msg>(); p.cand_sig = b.d_raw_in_cand_sig.as<double>();
     p.cand_line = b.d_raw_in_cand_line.as<uint32_t>(); p.cand_meta = b.d_raw_in_cand_meta.as<uint32_t>(); p.cand_cap = cand_cap;
-    p.gen_active = gen_active; p.gen_inactive = gen_inactive; p.first = b.d_raw_in_first.as<uint32_t>();
+    p.gen_active = r.gen_active; p.gen_inactive = r.gen_inactive; p.first = b.d_raw_in_first.as<uint32_t>();
     p.new_adds = b.d_raw_in_new_adds.as<uint32_t>(); p.kstar = kstar;
+    return MGPU_OK;
+}
+
+// The passes over ncand candidates, the bitmaps put back, the stream drained; misc[16] as launch_raw_in_resolve leaves it (zeros for no
+// candidates); the new adds appended to *adds and moved into the context's filter.  ncls: bytes of p.line_class to zero first.
+static int raw_in_resolve_end(mgpu_ctx *c, const RawInParams &p, const RawInResolve &r, uint64_t ncand, size_t ncls, unsigned long long *misc, std::vector<uint32_t> *adds) {
+    Behind &b = *c->behind;
+    memset(misc, 0, 16 * sizeof(unsigned long long));
+    if (ncand) {
+        unsigned long long *d_misc = b.d_raw_in_misc.as<unsigned long long>();
+        HIPCHK(c, hipMemsetAsync(d_misc, 0, 16 * sizeof(unsigned long long), c->stream_aux));
+        HIPCHK(c, hipMemsetAsync(d_misc + 8, 0xff, sizeof(unsigned long long), c->stream_aux));
+        if (ncls) HIPCHK(c, hipMemsetAsync(p.line_class, 0, ncls, c->stream_aux));
+        launch_raw_in_resolve(p, (uint32_t) ncand, b.d_raw_in_cb.as<uint32_t>(), b.d_raw_in_co.as<unsigned long long>(), d_misc, c->stream_aux);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(misc, d_misc, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream_aux));
+    } else if (ncls) HIPCHK(c, hipMemsetAsync(p.line_class, 0, ncls, c->stream_aux));
+    launch_raw_in_scatter(r.d_members, r.na, r.gen_active, 0, c->stream_aux);
+    launch_raw_in_scatter(r.d_members + r.na, r.ni, r.gen_inactive, 0, c->stream_aux);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    if (misc[9]) {                                              // the new adds, in the reference's order, into the context's filter
+        IcaoFilter &flt = c->resolver.filter();
+        const size_t at = adds->size();
+        adds->resize(at + misc[9]);
+        HIPCHK(c, hipMemcpy(adds->data() + at, p.new_adds, misc[9] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (size_t k = at; k < adds->size(); ++k) flt.add((*adds)[k]);
+    }
+    return MGPU_OK;
+}
+
+// a: text, msgs, line_of, signal_level, line_class device pointers, the capacities what this text may store (line_class indexed by
+// this text's own lines).  The counts of this text; the context's filter moved on by the text's new adds, which are appended to
+// *adds (the caller publishes them to the pre-screen's bitmap, or puts the filter back).
+static int raw_decode_passes(mgpu_ctx *c, const struct mgpu_raw_in_args &a, uint64_t line_base, RawInCounts *n, std::vector<uint32_t> *adds) {
+    Behind &b = *c->behind;
+    const size_t nb = (size_t) (a.nbytes / kUatTile + 2);
+    const uint64_t cand_cap = raw_in_max_cands(a.nbytes);
+    if (int rc = b.d_raw_in_meta.reserve(c, nb * kBlock * sizeof(uint16_t))) return rc;
+    if (int rc = b.d_raw_in_blocks.reserve(c, 5 * nb * sizeof(uint32_t))) return rc;
+    if (int rc = b.d_raw_in_off.reserve(c, 3 * nb * sizeof(unsigned long long))) return rc;
+    if (int rc = b.d_raw_in_total.reserve_exact(c, 8 * sizeof(unsigned long long))) return rc;
+    RawInParams p;
+    RawInResolve r;
+    if (int rc = raw_in_resolve_begin(c, cand_cap, p, r)) return rc;
+
+    const UatScratch w = {b.d_raw_in_meta.as<uint16_t>(), b.d_raw_in_blocks.as<uint32_t>(), b.d_raw_in_off.as<unsigned long long>(), b.d_raw_in_total.as<unsigned long long>(), nb};
+    p.text = a.text; p.nbytes = a.nbytes; p.now_ms = a.now_ms;
     p.msgs = a.msgs; p.line_of = (unsigned long long *) a.line_of; p.signal_level = a.signal_level; p.msgs_cap = a.msgs ? a.msgs_cap : 0;
     p.line_class = a.line_class; p.line_class_cap = a.line_class ? a.line_class_cap : 0; p.line_base = line_base;
     launch_raw_in_front(p, w, c->stream_aux);
@@ -1040,33 +1083,14 @@ static int raw_decode_passes(mgpu_ctx *c, const struct mgpu_raw_in_args &a, uint
     HIPCHK(c, hipMemcpyAsync(total, w.total, sizeof total, hipMemcpyDeviceToHost, c->stream_aux));
     HIPCHK(c, hipStreamSynchronize(c->stream_aux));
     unsigned long long misc[16];
-    memset(misc, 0, sizeof misc);
     int rc = MGPU_OK;
     const size_t ncls = p.line_class ? (size_t) std::min<uint64_t>(total[0], p.line_class_cap) : 0;   // "not a frame" is 0: only candidates store a class
     if (total[2] > cand_cap) { c->err = "raw decode: more candidates than the text can hold"; rc = MGPU_E_OVERFLOW; }   // (cannot happen: raw_in_max_cands)
-    else if (total[2]) {
-        unsigned long long *d_misc = b.d_raw_in_misc.as<unsigned long long>();
-        HIPCHK(c, hipMemsetAsync(d_misc, 0, sizeof misc, c->stream_aux));
-        HIPCHK(c, hipMemsetAsync(d_misc + 8, 0xff, sizeof(unsigned long long), c->stream_aux));
-        if (ncls) HIPCHK(c, hipMemsetAsync(p.line_class, 0, ncls, c->stream_aux));
-        launch_raw_in_resolve(p, (uint32_t) total[2], b.d_raw_in_cb.as<uint32_t>(), b.d_raw_in_co.as<unsigned long long>(), d_misc, c->stream_aux);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(misc, d_misc, sizeof misc, hipMemcpyDeviceToHost, c->stream_aux));
-    } else if (ncls) HIPCHK(c, hipMemsetAsync(p.line_class, 0, ncls, c->stream_aux));
-    launch_raw_in_scatter(d_members, na, gen_active, 0, c->stream_aux);
-    launch_raw_in_scatter(d_members + na, ni, gen_inactive, 0, c->stream_aux);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    if (int rc2 = raw_in_resolve_end(c, p, r, rc ? 0 : total[2], rc ? 0 : ncls, misc, adds)) return rc2;
     if (rc) return rc;
     n->lines = total[0]; n->consumed = total[1]; n->msgs = misc[10];
     for (int k = 1; k < 7; ++k) n->cn[k] = misc[k];
     n->cn[0] = misc[2] + misc[3] + misc[4] + misc[5] + misc[6];   // remote_received_modes: every Mode S line that reached the decode
-    if (misc[9]) {                                              // the new adds, in the reference's order, into the context's filter
-        const size_t at = adds->size();
-        adds->resize(at + misc[9]);
-        HIPCHK(c, hipMemcpy(adds->data() + at, p.new_adds, misc[9] * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (size_t k = at; k < adds->size(); ++k) flt.add((*adds)[k]);
-    }
     return MGPU_OK;
 }
 
@@ -1102,21 +1126,26 @@ static void raw_in_report(const struct mgpu_raw_in_args *a, const RawInCounts &n
 
 // the end of a call: on overflow the filter goes back to where it stood; otherwise the pre-screen learns the new addresses, as
 // mgpu_filter_add teaches it one (nothing is in flight behind the drain)
+// the pre-screen learns the addresses a call added to the filter, as mgpu_filter_add teaches it one (nothing is in flight behind the
+// drain); the raw input's and the beast input's
+static int raw_in_publish_adds(mgpu_ctx *c, const std::vector<uint32_t> &adds) {
+    if (adds.empty()) return MGPU_OK;
+    Behind &b = *c->behind;
+    if (int rc = b.d_raw_in_members.reserve(c, adds.size() * sizeof(uint32_t))) return rc;
+    HIPCHK(c, hipMemcpyAsync(b.d_raw_in_members.p, adds.data(), adds.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream_aux));
+    launch_raw_in_scatter(b.d_raw_in_members.as<uint32_t>(), (uint32_t) adds.size(), c->d_adder_bitmap, 1, c->stream_aux);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    return MGPU_OK;
+}
+
 static int raw_in_finish(mgpu_ctx *c, const struct mgpu_raw_in_args *a, const RawInCounts &n, const IcaoFilter::Snapshot &before, const std::vector<uint32_t> &adds) {
     if (n.msgs > a->msgs_cap || (a->line_class && n.lines > a->line_class_cap)) {
         c->resolver.filter().restore(before);
         c->err = n.msgs > a->msgs_cap ? "raw decode: more messages than the array holds" : "raw decode: more lines than line_class holds";
         return MGPU_E_OVERFLOW;
     }
-    if (!adds.empty()) {
-        Behind &b = *c->behind;
-        if (int rc = b.d_raw_in_members.reserve(c, adds.size() * sizeof(uint32_t))) return rc;
-        HIPCHK(c, hipMemcpyAsync(b.d_raw_in_members.p, adds.data(), adds.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream_aux));
-        launch_raw_in_scatter(b.d_raw_in_members.as<uint32_t>(), (uint32_t) adds.size(), c->d_adder_bitmap, 1, c->stream_aux);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream_aux));
-    }
-    return MGPU_OK;
+    return raw_in_publish_adds(c, adds);
 }
 
 int mgpu_raw_decode_device(mgpu_ctx *c, const struct mgpu_raw_in_args *a) {
@@ -1189,6 +1218,180 @@ int mgpu_raw_decode(mgpu_ctx *c, const struct mgpu_raw_in_args *a) {
     }
     raw_in_report(a, all);
     return raw_in_finish(c, a, all, before, adds);
+}
+
+// ---- Beast input: readBeast + decodeBinMessage over a binary stream (beast_in_format.h, kernels/beast_in.inc) ----
+
+// a: data and the per-message / per-call arrays device pointers, the capacities what this stretch may store (frame_class and frame_off
+// indexed by this stretch's own handler calls); frame_base and off_base are added to frame_of and frame_off.  final: the tail rule
+// applies.  The counts of this stretch; the filter moved on as in raw_decode_passes.
+static int beast_decode_passes(mgpu_ctx *c, const struct mgpu_beast_in_args &a, uint64_t frame_base, uint64_t off_base, bool final, BeastInCounts *n,
+                               std::vector<uint32_t> *adds) {
+    Behind &b = *c->behind;
+    const size_t tiles = beast_in_tiles(a.nbytes), groups = beast_in_groups(a.nbytes);
+    const uint64_t cand_cap = beast_in_max_msgs(a.nbytes);
+    if (int rc = b.d_bin_maps.reserve(c, tiles * 64)) return rc;
+    if (int rc = b.d_bin_gmaps.reserve(c, groups * 64)) return rc;
+    if (int rc = b.d_bin_entry.reserve(c, (tiles + groups) * sizeof(uint32_t))) return rc;
+    if (int rc = b.d_bin_marks.reserve(c, tiles * kBlock * sizeof(uint32_t))) return rc;
+    if (int rc = b.d_bin_meta.reserve(c, tiles * kBlock * sizeof(uint16_t))) return rc;
+    if (int rc = b.d_bin_lane_ids.reserve(c, tiles * kBlock * sizeof(uint64_t))) return rc;
+    if (int rc = b.d_bin_blocks.reserve(c, 6 * tiles * sizeof(uint32_t))) return rc;
+    if (int rc = b.d_bin_off.reserve(c, 2 * tiles * sizeof(uint64_t))) return rc;
+    if (int rc = b.d_bin_tile_id.reserve(c, tiles * sizeof(uint64_t))) return rc;
+    if (int rc = b.d_bin_entry_id.reserve(c, tiles * sizeof(uint64_t))) return rc;
+    if (int rc = b.d_bin_idflag.reserve(c, tiles * sizeof(uint32_t))) return rc;
+    if (int rc = b.d_bin_total.reserve_exact(c, 16 * sizeof(unsigned long long))) return rc;
+    if (int rc = b.d_bin_cand_id.reserve(c, cand_cap * sizeof(uint64_t))) return rc;
+    RawInParams p;
+    RawInResolve r;
+    if (int rc = raw_in_resolve_begin(c, cand_cap, p, r)) return rc;
+    p.text = a.data; p.nbytes = a.nbytes; p.now_ms = a.now_ms;
+    p.msgs = a.msgs; p.line_of = (unsigned long long *) a.frame_of; p.signal_level = a.signal_level; p.msgs_cap = a.msgs ? a.msgs_cap : 0;
+    p.line_class = a.frame_class; p.line_class_cap = a.frame_class ? a.frames_cap : 0; p.line_base = frame_base;
+    p.cand_id = b.d_bin_cand_id.as<unsigned long long>(); p.receiver_id = (unsigned long long *) a.receiver_id;
+    BeastInParams q;
+    q.data = a.data; q.nbytes = a.nbytes; q.net_ingest = a.net_ingest ? 1u : 0u; q.cfg = p.cfg; q.receiver_id_in = a.receiver_id_in;
+    q.cand_id = b.d_bin_cand_id.as<unsigned long long>();
+    q.frame_class = a.frame_class; q.frame_off = (unsigned long long *) a.frame_off; q.frames_cap = (a.frame_class || a.frame_off) ? a.frames_cap : 0; q.off_base = off_base;
+    const BeastInScratch w = {b.d_bin_maps.as<uint8_t>(), b.d_bin_gmaps.as<uint8_t>(), b.d_bin_entry.as<uint32_t>(), b.d_bin_marks.as<uint32_t>(), b.d_bin_meta.as<uint16_t>(),
+                              b.d_bin_lane_ids.as<unsigned long long>(), b.d_bin_blocks.as<uint32_t>(), b.d_bin_off.as<unsigned long long>(),
+                              b.d_bin_tile_id.as<unsigned long long>(), b.d_bin_entry_id.as<unsigned long long>(), b.d_bin_idflag.as<uint32_t>(),
+                              b.d_bin_total.as<unsigned long long>()};
+    launch_beast_in_front(q, p, w, c->stream_aux);
+    HIPCHK(c, hipGetLastError());
+    unsigned long long total[9];
+    HIPCHK(c, hipMemcpyAsync(total, w.total, sizeof total, hipMemcpyDeviceToHost, c->stream_aux));
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    unsigned long long misc[16];
+    int rc = MGPU_OK;
+    if (total[1] > cand_cap) { c->err = "beast decode: more candidates than the stream can hold"; rc = MGPU_E_OVERFLOW; }   // (cannot happen: beast_in_max_msgs)
+    // (every handler call's class is stored, by k_beast_in_classify or by the filter passes: nothing to zero)
+    if (int rc2 = raw_in_resolve_end(c, p, r, rc ? 0 : total[1], 0, misc, adds)) return rc2;
+    if (rc) return rc;
+    n->frames = total[0]; n->msgs = misc[10]; n->id = total[8];
+    uint64_t garbage = total[2];
+    if (total[6] != ~0ull) {
+        const uint64_t at = total[6] >> 8, delta = (total[6] >> 3) & 31u;
+        n->stop = (total[6] & 7u) == BEAST_IN_STOP_SYNTH ? MGPU_BEAST_STOP_SYNTH : MGPU_BEAST_STOP_UUID;
+        n->consumed = at + delta;
+    } else {
+        n->consumed = total[7];
+        if (final && a.nbytes - n->consumed > kBeastInTail) {   // net_io.c:5010-5015
+            garbage += a.nbytes - n->consumed;
+            n->consumed = a.nbytes;
+        }
+    }
+    n->stop_off = n->consumed;
+    n->cn[0] = misc[2] + misc[3] + misc[4] + misc[5] + misc[6];   // remote_received_modes: every Mode S frame that reached the decode
+    n->cn[1] = misc[1] + total[5];                              // remote_received_modeac: the records, and the frames dropped with mode_ac off
+    for (int k = 2; k < 7; ++k) n->cn[k] = misc[k];
+    n->cn[7] = garbage; n->cn[8] = total[4]; n->cn[9] = total[3];
+    return MGPU_OK;
+}
+
+static int beast_decode_dev(mgpu_ctx *c, const struct mgpu_beast_in_args &a, uint64_t frame_base, uint64_t off_base, bool final, BeastInCounts *n, std::vector<uint32_t> *adds) {
+    const int rc = beast_decode_passes(c, a, frame_base, off_base, final, n, adds);
+    if (rc != MGPU_OK) {                                        // (as raw_decode_dev: the tables are given up)
+        (void) hipStreamSynchronize(c->stream_aux);
+        c->behind->d_raw_in_first.release();
+        c->behind->d_raw_in_gen.release();
+    }
+    return rc;
+}
+
+static bool beast_in_args_ok(const struct mgpu_beast_in_args *a) {
+    if (!a || a->size < sizeof(struct mgpu_beast_in_args) || !a->consumed || !a->nframes || !a->nmsgs || !a->stop || !a->stop_off || !a->receiver_id_out || !a->counters) return false;
+    if (a->nbytes >= (1ull << 32) || a->msgs_cap > UINT64_MAX / sizeof(mgpu_msg) || a->frames_cap > UINT64_MAX / sizeof(uint64_t)) return false;
+    if (a->now_ms < 0 || a->now_ms >= 253402300800000ll) return false;
+    if (a->nbytes && !a->data) return false;
+    if ((a->msgs_cap && (!a->msgs || !a->receiver_id)) || (a->frames_cap && !a->frame_class && !a->frame_off)) return false;
+    return true;
+}
+
+static void beast_in_report(const struct mgpu_beast_in_args *a, const BeastInCounts &n) {
+    *a->consumed = n.consumed; *a->nframes = n.frames; *a->nmsgs = n.msgs; *a->stop = n.stop; *a->stop_off = n.stop_off; *a->receiver_id_out = n.id;
+    beast_in_counters_of(n, a->counters);
+}
+
+static int beast_in_finish(mgpu_ctx *c, const struct mgpu_beast_in_args *a, const BeastInCounts &n, const IcaoFilter::Snapshot &before, const std::vector<uint32_t> &adds) {
+    const bool want_frames = a->frame_class || a->frame_off;
+    if (n.msgs > a->msgs_cap || (want_frames && n.frames > a->frames_cap)) {
+        c->resolver.filter().restore(before);
+        c->err = n.msgs > a->msgs_cap ? "beast decode: more messages than the arrays hold" : "beast decode: more handler calls than the frame arrays hold";
+        return MGPU_E_OVERFLOW;
+    }
+    return raw_in_publish_adds(c, adds);                        // the pre-screen learns the new addresses, as after mgpu_raw_decode
+}
+
+int mgpu_beast_decode_device(mgpu_ctx *c, const struct mgpu_beast_in_args *a) {
+    if (!c || !beast_in_args_ok(a)) return MGPU_E_INVAL;
+    if (((uintptr_t) a->msgs | (uintptr_t) a->receiver_id | (uintptr_t) a->frame_of | (uintptr_t) a->signal_level | (uintptr_t) a->frame_off) & 7u) return MGPU_E_INVAL;
+    BeastInCounts n;
+    n.id = a->receiver_id_in;
+    beast_in_report(a, n);
+    if (a->nbytes == 0) return MGPU_OK;
+    { const int rc = drain(c); if (rc != MGPU_OK) return rc; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    IcaoFilter::Snapshot before;
+    c->resolver.filter().snapshot(before);
+    std::vector<uint32_t> adds;
+    if (int rc = beast_decode_dev(c, *a, 0, 0, true, &n, &adds)) { c->resolver.filter().restore(before); return rc; }
+    beast_in_report(a, n);
+    return beast_in_finish(c, a, n, before, adds);
+}
+
+int mgpu_beast_decode(mgpu_ctx *c, const struct mgpu_beast_in_args *a) {
+    if (!c || !beast_in_args_ok(a)) return MGPU_E_INVAL;
+    BeastInCounts all;
+    all.id = a->receiver_id_in;
+    beast_in_report(a, all);
+    if (a->nbytes == 0) return MGPU_OK;
+    { const int rc = drain(c); if (rc != MGPU_OK) return rc; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    Behind &b = *c->behind;
+    IcaoFilter::Snapshot before;
+    c->resolver.filter().snapshot(before);
+    std::vector<uint32_t> adds;
+    const bool want_frames = a->frame_class || a->frame_off;
+    size_t adds_before = 0;
+    IcaoFilter::Snapshot pass_before;
+    const int prc = beast_in_passes(a->nbytes, a->pass_bytes ? a->pass_bytes : kUatDefaultPass, all,
+        [&](uint64_t at, uint64_t nb, bool final, const BeastInCounts &so_far, BeastInCounts &n) -> int {
+            // what this pass may write: what the caller's arrays still hold, and no more than nb bytes can give
+            const uint64_t msg_room = a->msgs_cap > so_far.msgs ? std::min<uint64_t>(a->msgs_cap - so_far.msgs, beast_in_max_msgs(nb)) : 0;
+            const uint64_t frame_room = want_frames && a->frames_cap > so_far.frames ? std::min<uint64_t>(a->frames_cap - so_far.frames, beast_in_max_frames(nb)) : 0;
+            int rc;
+            if ((rc = b.d_bin_data.reserve(c, nb + 64)) || (rc = b.d_bin_msgs.reserve(c, (msg_room + 1) * sizeof(mgpu_msg))) ||
+                (rc = b.d_bin_ids.reserve(c, (msg_room + 1) * sizeof(uint64_t))) || (rc = b.d_bin_frame_of.reserve(c, (msg_room + 1) * sizeof(uint64_t))) ||
+                (rc = b.d_bin_sig.reserve(c, (msg_room + 1) * sizeof(double))) || (rc = b.d_bin_cls.reserve(c, frame_room + 1)) ||
+                (rc = b.d_bin_frame_off.reserve(c, (frame_room + 1) * sizeof(uint64_t)))) return rc;
+            struct mgpu_beast_in_args d = *a;
+            d.data = b.d_bin_data.as<uint8_t>(); d.nbytes = nb; d.receiver_id_in = so_far.id;
+            d.msgs = b.d_bin_msgs.as<mgpu_msg>(); d.receiver_id = b.d_bin_ids.as<uint64_t>(); d.msgs_cap = msg_room;
+            d.frame_of = a->frame_of ? b.d_bin_frame_of.as<uint64_t>() : nullptr;
+            d.signal_level = a->signal_level ? b.d_bin_sig.as<double>() : nullptr;
+            d.frame_class = a->frame_class ? b.d_bin_cls.as<uint8_t>() : nullptr;
+            d.frame_off = a->frame_off ? b.d_bin_frame_off.as<uint64_t>() : nullptr;
+            d.frames_cap = frame_room;
+            HIPCHK(c, hipMemcpyAsync(b.d_bin_data.p, a->data + at, nb, hipMemcpyHostToDevice, c->stream_aux));
+            adds_before = adds.size();
+            c->resolver.filter().snapshot(pass_before);
+            if ((rc = beast_decode_dev(c, d, so_far.frames, at, final, &n, &adds))) return rc;
+            // (the pass stored below its rooms only: the copies stay inside the caller's arrays)
+            const uint64_t nmsg = std::min<uint64_t>(n.msgs, msg_room), nfr = std::min<uint64_t>(n.frames, frame_room);
+            if (nmsg) HIPCHK(c, hipMemcpy(a->msgs + so_far.msgs, d.msgs, nmsg * sizeof(mgpu_msg), hipMemcpyDeviceToHost));
+            if (nmsg) HIPCHK(c, hipMemcpy(a->receiver_id + so_far.msgs, d.receiver_id, nmsg * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            if (nmsg && a->frame_of) HIPCHK(c, hipMemcpy(a->frame_of + so_far.msgs, d.frame_of, nmsg * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            if (nmsg && a->signal_level) HIPCHK(c, hipMemcpy(a->signal_level + so_far.msgs, d.signal_level, nmsg * sizeof(double), hipMemcpyDeviceToHost));
+            if (nfr && a->frame_class) HIPCHK(c, hipMemcpy(a->frame_class + so_far.frames, d.frame_class, nfr, hipMemcpyDeviceToHost));
+            if (nfr && a->frame_off) HIPCHK(c, hipMemcpy(a->frame_off + so_far.frames, d.frame_off, nfr * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            return MGPU_OK;
+        },
+        [&] { c->resolver.filter().restore(pass_before); adds.resize(adds_before); });
+    if (prc != MGPU_OK) { c->resolver.filter().restore(before); return prc; }
+    beast_in_report(a, all);
+    return beast_in_finish(c, a, all, before, adds);
 }
 
 // ---- ASTERIX input: readAsterix + decodeAsterixMessage over a length-chained stream (asterix_in_format.h, kernels/asterix_in.inc) ----

@@ -55,6 +55,11 @@ struct Behind {
     DevBuf d_raw_in_meta, d_raw_in_blocks, d_raw_in_off, d_raw_in_total, d_raw_in_cand_rec, d_raw_in_cand_sig, d_raw_in_cand_line, d_raw_in_cand_meta, d_raw_in_new_adds;
     DevBuf d_raw_in_cb, d_raw_in_co, d_raw_in_misc, d_raw_in_first, d_raw_in_gen, d_raw_in_members, d_raw_in_crc;
     DevBuf d_raw_in_text, d_raw_in_msgs, d_raw_in_line_of, d_raw_in_sig, d_raw_in_cls;
+    // Beast input (kernels/beast_in.inc): the tiles' and the groups' exit maps, the entries, the chain's bitmap; per lane a halfword and
+    // an id; per tile six words, two offsets, an id set, an id in force and a flag; the nine totals; per candidate the id in force (the
+    // other candidate arrays and the filter's tables are the raw input's); the host-array form's staged stream and results
+    DevBuf d_bin_maps, d_bin_gmaps, d_bin_entry, d_bin_marks, d_bin_meta, d_bin_lane_ids, d_bin_blocks, d_bin_off, d_bin_tile_id, d_bin_entry_id, d_bin_idflag, d_bin_total;
+    DevBuf d_bin_cand_id, d_bin_data, d_bin_msgs, d_bin_ids, d_bin_sig, d_bin_frame_of, d_bin_cls, d_bin_frame_off;
     // ASTERIX input (kernels/asterix_in.inc): the tiles' and the groups' exit maps; the entries; three bitmaps per tile; per tile four
     // words and two offsets; the nine totals; the host-array form's staged stream and its results
     DevBuf d_ast_in_maps, d_ast_in_gmaps, d_ast_in_entry, d_ast_in_bits, d_ast_in_blocks, d_ast_in_off, d_ast_in_total, d_ast_in_data, d_ast_in_recs, d_ast_in_frame_of;

@@ -19,6 +19,7 @@
 
 #include "../../include/modes_gpu.h"   // struct mgpu_msg (the beast encoder reads it on the device)
 #include "raw_in_format.h"
+#include "beast_in_format.h"
 
 namespace mgpu {
 
@@ -348,10 +349,45 @@ struct RawInParams {
     uint8_t *line_class;              // optional: nothing at or beyond line_class + line_class_cap is stored
     uint64_t line_class_cap;
     uint64_t line_base;               // added to every line_of (the host form's passes)
+    const unsigned long long *cand_id = nullptr;   // the beast input: per candidate the receiver id in force, and where the accepted
+    unsigned long long *receiver_id = nullptr;     // ones' go (msgs_cap entries); both null for the raw input
 };
 void launch_raw_in_scatter(const uint32_t *members, uint32_t n, uint32_t *bitmap, int set, hipStream_t s);
 void launch_raw_in_front(const RawInParams &a, const UatScratch &w, hipStream_t s);
 void launch_raw_in_resolve(const RawInParams &a, uint32_t ncand, uint32_t *cb, unsigned long long *co, unsigned long long *misc, hipStream_t s);
+// Beast input (kernels/beast_in.inc; readBeast + decodeBinMessage over a binary stream, beast_in_format.h): the UAT input's tiles; a
+// step reaches at most 62 bytes, so the chain that passes a tile enters the next at one of its first 64 offsets.  It ends in the raw
+// input's candidate arrays and filter passes (RawInParams: a "line" is a handler call)
+constexpr uint32_t kBeastInGroup = 64;        // tiles whose exit maps are composed into one
+constexpr size_t beast_in_tiles(uint64_t nbytes) { return (size_t) (nbytes / kUatTile + 1); }   // (the chain may end AT nbytes)
+constexpr size_t beast_in_groups(uint64_t nbytes) { return (beast_in_tiles(nbytes) + kBeastInGroup - 1) / kBeastInGroup; }
+struct BeastInParams {
+    const uint8_t *data;              // any alignment
+    uint64_t nbytes;
+    uint32_t net_ingest;
+    RawInConfig cfg;
+    uint64_t receiver_id_in;
+    unsigned long long *cand_id;      // cand_cap entries beside RawInParams' candidate arrays
+    uint8_t *frame_class;             // optional: the classes the filter does not decide; nothing at or beyond frames_cap is stored
+    unsigned long long *frame_off;    // optional
+    uint64_t frames_cap;
+    uint64_t off_base;                // added to every frame_off (the host form's passes)
+};
+struct BeastInScratch {
+    uint8_t *maps;                    // [tiles * 64] a tile's exit map: entry offset -> entry offset of the next tile, 0xff: the chain ends here
+    uint8_t *gmaps;                   // [groups * 64] the same over a group of tiles
+    uint32_t *entry;                  // [tiles + groups] where the chain from 0 enters each tile (kNone: it does not), then each group
+    uint32_t *marks;                  // [tiles * kBlock] the chain's offsets, a bit per byte
+    uint16_t *meta;                   // [tiles * kBlock] per lane: handler calls | candidates << 4 | an id set << 15
+    unsigned long long *lane_ids;     // [tiles * kBlock] the last id a lane's steps set
+    uint32_t *blocks;                 // [6 * tiles] per tile: handler calls | candidates | garbage | commands | ids taken | Mode A/C dropped
+    unsigned long long *off;          // [2 * tiles] the exclusive prefix sums of the first two
+    unsigned long long *tile_id;      // [tiles] the last id a tile's steps set, [tiles] the id in force at its start
+    unsigned long long *entry_id;
+    uint32_t *tile_idflag;            // [tiles]
+    unsigned long long *total;        // [9] see launch_beast_in_front
+};
+void launch_beast_in_front(const BeastInParams &a, const RawInParams &p, const BeastInScratch &w, hipStream_t s);
 // ASTERIX input (kernels/asterix_in.inc; readAsterix + decodeAsterixMessage over a length-chained stream, asterix_in_format.h)
 constexpr uint32_t kAstTile = 65536;          // bytes per tile: a length is below 65536, so a chain that enters tile t leaves it into tile t + 1
 constexpr uint32_t kAstGroup = 32;            // tiles whose exit maps are composed into one

@@ -18,6 +18,8 @@
 //   k_sbs_in_*       `--net-sbs-in-port` and the MLAT / JAERO / PRIO ports: BaseStation lines to aircraft records (net_io.c:2952-3178)
 //   k_raw_in_*       `--net-ri-port`: AVR raw lines to accepted messages, the ICAO filter's answers resolved in parallel (net_io.c:4104-4317,
 //                    mode_s.c:443-606, 766-779)
+//   k_beast_in_*     `--net-bi-port`: a beast binary stream to accepted messages with their receiver ids, readBeast's escape-and-resync
+//                    framing as composed tile maps, then the raw input's decode and filter passes (net_io.c:4737-5018, 3804-3961)
 //   k_ast_in_*       `--net-asterix-in-port`: a length-chained stream of CAT021 records to aircraft records (net_io.c:4643-4659, 1922-2407)
 //
 // No MFMA anywhere: this is HBM-bound integer/byte streaming work.  All arithmetic on the
@@ -141,6 +143,7 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 #include "kernels/uat.inc"
 #include "kernels/sbs_in.inc"
 #include "kernels/raw_in.inc"
+#include "kernels/beast_in.inc"
 #include "kernels/asterix_in.inc"
 #include "kernels/fields.inc"
 #include "kernels/gate.inc"

@@ -114,7 +114,9 @@ __global__ __launch_bounds__(kBlock) void k_raw_in_first(RawInParams a, uint32_t
     const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
     if (j >= ncand) return;
     const uint32_t m = a.cand_meta[j];
-    if (m & kRawMetaAdder) atomicMin(a.first + (m & kRawMetaAddr), j);
+    // (a value only falls during this pass: an entry read at or below j stays there, and the atomic would change nothing — with few
+    // aircraft and many frames nearly every adder ends here instead of queueing on its address's word)
+    if ((m & kRawMetaAdder) && a.first[m & kRawMetaAddr] > j) atomicMin(a.first + (m & kRawMetaAddr), j);
 }
 
 __device__ __forceinline__ bool raw_in_new_add(const RawInParams &a, uint32_t j, uint32_t ncand, uint32_t &addr) {
@@ -213,6 +215,7 @@ __global__ __launch_bounds__(kBlock) void k_raw_in_write(RawInParams a, uint32_t
         for (int k = 0; k < 8; ++k) dst[k] = src[k];
         if (a.line_of) a.line_of[out] = a.line_base + line;
         if (a.signal_level) a.signal_level[out] = a.cand_sig[j];
+        if (a.receiver_id) a.receiver_id[out] = a.cand_id[j];              // (the beast input)
     }
 }
 

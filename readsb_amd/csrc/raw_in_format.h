@@ -127,6 +127,87 @@ RAW_IN_HD void raw_in_zero(RawInLine &o) {
     o.signal = 0.0; o.cls = MGPU_RAW_NONE; o.addr = 0; o.adder = 0;
 }
 
+// The tail both inputs share (the beast input, beast_in_format.h, calls it too): a frame's bytes m[0..nbytes), nbytes 2, 7 or 14 and the
+// rest zero, its timestamp, mm->signalLevel and the beast signal byte, to the record and the class: decodeModeAMessage, or
+// decodeModesMessage (mode_s.c:443-606).  out is zeroed (raw_in_zero) by the caller.  Returns out.cls.
+RAW_IN_HD uint32_t raw_in_decode_frame(uint8_t *m, uint32_t nbytes, uint64_t ts, double signal, uint32_t sig_byte, int64_t now_ms, const RawInConfig &cfg,
+                                       const RawInTables &tb, RawInLine &out) {
+    mgpu_msg &r = out.msg;
+    r.timestamp = (int64_t) ts;
+    r.sysTimestamp = now_ms;
+    r.sig_sumsq = (uint64_t) (257u * sig_byte) * (257u * sig_byte);
+    r.sig_len = 1;
+    out.signal = signal;
+    for (int i = 0; i < 14; ++i) r.raw[i] = m[i];
+
+    if (nbytes == 2) {                                                       // decodeModeAMessage, mode_ac.c:165-200
+        r.msgtype = 77;
+        r.msgbits = 16;
+        r.msg[0] = m[0]; r.msg[1] = m[1];
+        r.addr = ((uint32_t) m[0] << 8 | m[1]) & 0xFF7Fu;                // low 24 bits of (ModeA & 0xFF7F) | MODES_NON_ICAO_ADDRESS
+        out.addr = r.addr;
+        return out.cls = MGPU_RAW_MODEAC;
+    }
+
+    // decodeModesMessage, mode_s.c:443-606
+    uint32_t cls = MGPU_RAW_BAD, addr = 0, adder = 0, corrected = 0;
+    uint32_t df = m[0] >> 3;
+    bool zero = true;
+    for (int i = 0; i < 7; ++i) zero = zero && m[i] == 0;
+    if (!zero) {
+        if (cfg.fixDF && cfg.nfix_crc && (df == 1 || df == 25 || df == 21 || df == 19 || df == 16)) {    // fixDF17msgtype, :276-301
+            const uint8_t orig = m[0];
+            m[0] = (uint8_t) ((orig & 7u) | (17u << 3));
+            if (raw_in_crc(m, 112, tb.crc_byte) == 0) { df = 17; corrected = 1; } else m[0] = orig;
+        }
+        const uint32_t bits = (df & 0x10u) ? 112u : 56u;
+        const uint32_t crc = raw_in_crc(m, bits, tb.crc_byte);
+        uint32_t b0 = 0xff, b1 = 0xff;
+        r.msgbits = (uint8_t) bits;
+        if (df == 0 || df == 4 || df == 5 || df == 16 || df == 20 || df == 21 || df >= 24) {             // Address/Parity
+            cls = MGPU_RAW_COND;
+            addr = crc;
+        } else if (df == 11) {
+            if (crc & 0xffff80u) {
+                const int ne = raw_in_diagnose(tb.tab_short, tb.n_short, crc, b0, b1);
+                if (ne == 1) {                                           // (two-bit errors are ambiguous in DF11)
+                    corrected = 1;
+                    m[b0 >> 3] ^= (uint8_t) (0x80u >> (b0 & 7u));
+                    cls = MGPU_RAW_COND;
+                    addr = raw_in_aa(m);
+                }
+            } else {
+                cls = MGPU_RAW_ACCEPT;
+                addr = raw_in_aa(m);
+                adder = (crc & 0x7fu) == 0;
+            }
+        } else if (df == 17 || df == 18) {
+            if (crc != 0) {
+                const int ne = raw_in_diagnose(tb.tab_long, tb.n_long, crc, b0, b1);
+                if (ne >= 1) {
+                    const uint32_t addr1 = raw_in_aa(m);
+                    corrected = (uint32_t) ne;
+                    m[b0 >> 3] ^= (uint8_t) (0x80u >> (b0 & 7u));
+                    if (ne == 2) m[b1 >> 3] ^= (uint8_t) (0x80u >> (b1 & 7u));
+                    addr = raw_in_aa(m);
+                    cls = addr1 != addr ? MGPU_RAW_COND : MGPU_RAW_ACCEPT;
+                }
+            } else {
+                cls = MGPU_RAW_ACCEPT;
+                addr = raw_in_aa(m);
+                adder = df == 17 && corrected == 0;
+            }
+        }
+    }
+    r.correctedbits = (uint8_t) corrected;
+    r.msgtype = (uint8_t) df;
+    r.addr = addr;
+    for (int i = 0; i < 14; ++i) r.msg[i] = m[i];
+    out.addr = addr;
+    out.adder = adder;
+    return out.cls = cls;
+}
+
 // One line.  Returns out.cls.
 RAW_IN_HD uint32_t raw_in_line(const uint8_t *p, uint32_t n, int64_t now_ms, const RawInConfig &cfg, const RawInTables &tb, RawInLine &out) {
     raw_in_zero(out);
@@ -220,80 +301,7 @@ RAW_IN_HD uint32_t raw_in_line(const uint8_t *p, uint32_t n, int64_t now_ms, con
         m[j / 2] = (uint8_t) (hi << 4 | lo);
     }
 
-    mgpu_msg &r = out.msg;
-    r.timestamp = (int64_t) ts;
-    r.sysTimestamp = now_ms;
-    r.sig_sumsq = (uint64_t) (257u * sig_byte) * (257u * sig_byte);
-    r.sig_len = 1;
-    out.signal = signal;
-    for (int i = 0; i < 14; ++i) r.raw[i] = m[i];
-
-    if (fl == 4) {                                                       // decodeModeAMessage, mode_ac.c:165-200
-        r.msgtype = 77;
-        r.msgbits = 16;
-        r.msg[0] = m[0]; r.msg[1] = m[1];
-        r.addr = ((uint32_t) m[0] << 8 | m[1]) & 0xFF7Fu;                // low 24 bits of (ModeA & 0xFF7F) | MODES_NON_ICAO_ADDRESS
-        out.addr = r.addr;
-        return out.cls = MGPU_RAW_MODEAC;
-    }
-
-    // decodeModesMessage, mode_s.c:443-606
-    uint32_t cls = MGPU_RAW_BAD, addr = 0, adder = 0, corrected = 0;
-    uint32_t df = m[0] >> 3;
-    bool zero = true;
-    for (int i = 0; i < 7; ++i) zero = zero && m[i] == 0;
-    if (!zero) {
-        if (cfg.fixDF && cfg.nfix_crc && (df == 1 || df == 25 || df == 21 || df == 19 || df == 16)) {    // fixDF17msgtype, :276-301
-            const uint8_t orig = m[0];
-            m[0] = (uint8_t) ((orig & 7u) | (17u << 3));
-            if (raw_in_crc(m, 112, tb.crc_byte) == 0) { df = 17; corrected = 1; } else m[0] = orig;
-        }
-        const uint32_t bits = (df & 0x10u) ? 112u : 56u;
-        const uint32_t crc = raw_in_crc(m, bits, tb.crc_byte);
-        uint32_t b0 = 0xff, b1 = 0xff;
-        r.msgbits = (uint8_t) bits;
-        if (df == 0 || df == 4 || df == 5 || df == 16 || df == 20 || df == 21 || df >= 24) {             // Address/Parity
-            cls = MGPU_RAW_COND;
-            addr = crc;
-        } else if (df == 11) {
-            if (crc & 0xffff80u) {
-                const int ne = raw_in_diagnose(tb.tab_short, tb.n_short, crc, b0, b1);
-                if (ne == 1) {                                           // (two-bit errors are ambiguous in DF11)
-                    corrected = 1;
-                    m[b0 >> 3] ^= (uint8_t) (0x80u >> (b0 & 7u));
-                    cls = MGPU_RAW_COND;
-                    addr = raw_in_aa(m);
-                }
-            } else {
-                cls = MGPU_RAW_ACCEPT;
-                addr = raw_in_aa(m);
-                adder = (crc & 0x7fu) == 0;
-            }
-        } else if (df == 17 || df == 18) {
-            if (crc != 0) {
-                const int ne = raw_in_diagnose(tb.tab_long, tb.n_long, crc, b0, b1);
-                if (ne >= 1) {
-                    const uint32_t addr1 = raw_in_aa(m);
-                    corrected = (uint32_t) ne;
-                    m[b0 >> 3] ^= (uint8_t) (0x80u >> (b0 & 7u));
-                    if (ne == 2) m[b1 >> 3] ^= (uint8_t) (0x80u >> (b1 & 7u));
-                    addr = raw_in_aa(m);
-                    cls = addr1 != addr ? MGPU_RAW_COND : MGPU_RAW_ACCEPT;
-                }
-            } else {
-                cls = MGPU_RAW_ACCEPT;
-                addr = raw_in_aa(m);
-                adder = df == 17 && corrected == 0;
-            }
-        }
-    }
-    r.correctedbits = (uint8_t) corrected;
-    r.msgtype = (uint8_t) df;
-    r.addr = addr;
-    for (int i = 0; i < 14; ++i) r.msg[i] = m[i];
-    out.addr = addr;
-    out.adder = adder;
-    return out.cls = cls;
+    return raw_in_decode_frame(m, (uint32_t) fl / 2u, ts, signal, sig_byte, now_ms, cfg, tb, out);
 }
 
 }  // namespace mgpu
