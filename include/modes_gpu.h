@@ -60,7 +60,16 @@ struct mgpu_config {
     uint32_t trailing_samples;    /* Modes.trailing_samples = 326 (readsb.c:288); must be 326 */
     uint32_t mode_ac;             /* Modes.mode_ac (--modeac): also run demodulate2400AC on every buffer, readsb.c:871-874.  Every
                                    * format: its noise floor comes from the buffer's mean level / power, which for SC16 / SC16Q11 are
-                                   * the reference's sequential float sums (convert.c:225-249), reproduced bit for bit. */
+                                   * the reference's sequential float sums (convert.c:225-249), reproduced bit for bit.
+                                   * Capacity: the scan works on a pipeline chunk (max_samples rounded up to whole buffers, at most
+                                   * chunk_buffers of them) in tiles of 2048 positions and appends a tile's candidates (the positions
+                                   * that pass every test of the loop body, before the skip over an accepted reply) to list
+                                   * (tile mod 64) of 64 lists, each with room for (chunk samples / 256 + 65536) / 64 candidates: 1032
+                                   * with a chunk of one buffer, where a list serves one tile and a tile has at most 1024, so that
+                                   * nothing can overflow; 1536 with 64 buffers, 2560 with 1024.  Larger chunks are sized for one
+                                   * reply per 256 samples: a chunk that gives one list more than its room (replies packed 70
+                                   * samples apart over 64 buffers do) fails its feed with MGPU_E_OVERFLOW; no reply is ever
+                                   * dropped without that error, and mgpu_reset leaves the context usable again. */
     uint64_t max_samples;         /* largest number of new samples one mgpu_feed_* call may carry */
     int64_t  startup_time_ms;     /* Modes.startup_time: wall clock (ms) the 12 MHz sample clock is anchored to */
     uint64_t record_pool_records; /* device pool for per-phase candidate records; 0 = max_samples/16 + 65536 */
