@@ -80,7 +80,7 @@ int beast_in_decode_sequential(const struct mgpu_beast_in_args *a, const struct 
     BeastInCounts all;
     all.id = a->receiver_id_in;
     if (a->nbytes)
-        (void) beast_in_passes(a->nbytes, a->pass_bytes, all,
+        (void) stream_passes(a->nbytes, a->pass_bytes, false, all,
             [&](uint64_t at, uint64_t nb, bool final, const BeastInCounts &so_far, BeastInCounts &n) {
                 flt.snapshot(pass_before);
                 struct mgpu_beast_in_args d = *a;

@@ -1,4 +1,4 @@
-// ctx.h — private to the library: what the translation units behind the C ABI (api.cpp, affinity.cpp, shard.cpp, behind.cpp) share —
+// ctx.h — private to the library: what the translation units behind the C ABI (api.cpp, affinity.cpp, shard.cpp, behind_out.cpp, behind_in.cpp) share —
 // the context, its slots and jobs, and the few functions that cross files.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // dump_format.h — the decoded-message dump of displayModesMessage (mode_s.c:1809-2239) with the line printACASInfoShort adds
 // (json_out.c:443-629, a == NULL), restated from its formats: ONE formatter, __host__ __device__ and templated on the sink, for the
-// counting pass and the writing pass of kernels/dump.inc and for the host (behind.cpp: mgpu_dump_format_host;
+// counting pass and the writing pass of kernels/dump.inc and for the host (behind_out.cpp: mgpu_dump_format_host;
 // tests/host_stub/dump_format_check.cpp runs it against the reference's bytes under ASan and UBSan).  The three cannot disagree
 // about a length.
 //

@@ -1,5 +1,5 @@
 // icao_filter.h — the ICAO address filter of the reference (icao_filter.c) as an exact model, free of the device headers: the ordered
-// walk (resolve.h), the raw input's replay of the device's new adds (behind.cpp) and its sequential resolver and check programs
+// walk (resolve.h), the raw input's replay of the device's new adds (behind_in.cpp) and its sequential resolver and check programs
 // (raw_in_host.cpp, tests/host_stub/raw_in_*_check.cpp, plain g++) all use this one.  Header only, so that each of them is one
 // translation unit more and no more.
 #pragma once

@@ -1,6 +1,6 @@
 // uat_host.cpp — the UAT formatter (uat_format.h) on the host: mgpu_uat_format_host / mgpu_uat_format_line_host, which settle the
 // lines the device defers with the host's sscanf and libm, and the one cached table of signal bytes (mgpu::uat_sig_table) that the
-// host formatter reads and behind.cpp uploads for the device.  No HIP in this file:
+// host formatter reads and behind_in.cpp uploads for the device.  No HIP in this file:
 // tests/host_stub/uat_format_check.cpp compiles it with plain g++, under ASan and UBSan too.
 #include <cstring>
 #include <vector>
@@ -8,7 +8,7 @@
 #include "uat_format.h"
 
 namespace mgpu {
-// the one table of signal bytes, built on first use: the host formatter reads it here, behind.cpp uploads it for the device
+// the one table of signal bytes, built on first use: the host formatter reads it here, behind_in.cpp uploads it for the device
 const uint8_t *uat_sig_table() {
     static const std::vector<uint8_t> table = [] {
         std::vector<uint8_t> t(kUatSigTable);

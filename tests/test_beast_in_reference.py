@@ -199,7 +199,7 @@ def test_host_walk_through_the_library(lib, golden):
 
 
 def test_passes_give_the_whole_call(lib, golden):
-    """The passes of the host form (beast_in_passes, here over the sequential walk) with pass_bytes small enough to cut inside frames,
+    """The passes of the host form (stream_passes, here over the sequential walk) with pass_bytes small enough to cut inside frames,
     inside prefixes and inside runs of garbage: exactly the result of one call over the whole stream."""
     import readsb_amd.binding as rb
     rng = np.random.default_rng(8)
