@@ -1589,6 +1589,103 @@ int mgpu_beast_decode_device(mgpu_ctx *ctx, const struct mgpu_beast_in_args *arg
  * nbytes).  Needs no context and no GPU. */
 int mgpu_beast_parse_host(const uint8_t *data, uint64_t nbytes, uint64_t offset, int64_t now_ms, const struct mgpu_beast_in_config *cfg, struct mgpu_beast_in_frame *out);
 
+/* ---- Planefinder input: a DLE-framed binary stream to accepted message records (`--net-pfms-in-port`, the planefinder_in
+ * connector; readPlanefinder, net_io.c:4670-4735, with decodePfMessage, :3995-4101, as its read handler and getNextPfUnstuffedByte,
+ * :3965-3970; kernels/pf_in.inc, pf_in_format.h) ------------
+ * One call is one readPlanefinder over [data, data + nbytes) with now = now_ms.  DLE = 0x10, ETX = 0x03.
+ *   The framer, quirk for quirk: from som, memchr finds the next DLE at p.  It is a frame start iff p + 1 < nbytes and data[p + 1] is
+ *     neither DLE nor ETX; any other DLE moves som to p + 1 (a DLE in the buffer's last byte is consumed).  From start + 2 the end is
+ *     the first q with data[q] == DLE, q + 1 < nbytes and data[q + 1] == ETX (`DLE DLE ETX` in a stuffed body ends the frame at its
+ *     second DLE).  Without an end the call returns with som where it stood before this start was found; with one, som = q + 2, and
+ *     the handler is called iff data[start + 1] == 0xc1 (any other packet id, the 0x41 of the reference's comment included, is
+ *     skipped and counted in nskipped).  A frame has no bounded length.
+ *   The handler does not respect the frame's end: it skips the start DLE and reads unstuffed bytes (a DLE is dropped and the byte
+ *     behind it taken, whatever it is), at most 53 bytes from the start, through the end marker and the frames behind it if need be:
+ *     the id, a padding byte, a type byte t — t & 0xF == 0 Mode A/C with 2 bytes (with cfg.mode_ac off it returns WITHOUT counting:
+ *     the beast input counts this case), 1 and 2 Mode S with 7 and 14, anything else returns — a signal byte b with signalLevel =
+ *     (b / 255.0)^2 in two double operations, four bytes of seconds and four of nanoseconds, big endian, timestamp = seconds *
+ *     1000000000 + nanoseconds, sysTimestamp = now_ms, then the message bytes.  Then decodeModeAMessage, or the decode and the filter
+ *     question of the raw input (above), the filter moved on and the pre-screen taught as there.  A record is what mgpu_raw_decode
+ *     leaves: raw the bytes as unstuffed, sig_sumsq = (257 b)^2, sig_len 1.  mm->receiverId stays 0: there are no receiver ids.
+ *   Reads behind the buffer: every byte at an index >= nbytes reads as 0 (the reference puts a NUL at data[nbytes] and reads what
+ *     earlier reads left behind it); nothing at or beyond nbytes is loaded.  counters->past_end counts the handler calls whose decode
+ *     read an index > nbytes: for those the result is one of the results the reference can give, not the only one.
+ *   A caller that feeds a stream block by block stays exact with args->look: that many bytes at data[nbytes ..) are the stream's too.
+ *     They are not framed — only a DLE below nbytes is an event — but they are the lookahead of the DLE in the last byte and what a
+ *     handler call reads behind nbytes, and the end that past_end counts against is nbytes + look.  With look >= 53 (or everything
+ *     that is left of the stream) and the remainder from *consumed carried, the calls give exactly what one call over the whole
+ *     stream gives; *consumed can then be nbytes + 1 (a frame's ETX in data[nbytes]).  readsb_gpu_pf_in.c reads this way.
+ *   Not modelled: debug_planefinder, unreasonable_messagerate, receiverCheckBad; netUseMessage and beyond.  Rejected messages leave
+ *     no record.
+ *   Per message, in stream order: msgs, signal_level (optional), frame_of (optional: the handler call that gave it).  Per handler
+ *     call (optional, frames_cap entries): frame_class (MGPU_PF_IN_*) and frame_off (the offset of the frame's start DLE).
+ *   Bounds: a handler call needs 4 bytes, so *nframes <= nbytes / 4 and *nmsgs <= *nframes.
+ *   args->size smaller than sizeof(struct mgpu_pf_in_args), a NULL ctx, args, consumed, nframes, nmsgs or counters, data NULL with
+ *     nbytes != 0, msgs NULL with msgs_cap != 0, frame_class and frame_off both NULL with frames_cap != 0, nbytes + look >= 2^32, now_ms
+ *     outside [0, 253402300800000): MGPU_E_INVAL.  nbytes == 0: MGPU_OK with zeros.  More messages than msgs_cap, or (with frame_class
+ *     or frame_off) more handler calls than frames_cap: MGPU_E_OVERFLOW with *nmsgs and *nframes = what is needed; nothing is stored
+ *     at or beyond a capacity, and the filter and the pre-screen stay where they stood.  The calls drain the pipeline first.
+ *   mgpu_pf_decode: every array in host memory; the stream is staged in passes of pass_bytes (0: the library's default) with the 53
+ *     bytes behind each, a pass cut at the som it reached (a pass that is not the last judges the DLE in its last byte by the byte
+ *     behind it), the remainder and the filter carried, past_end counted against the real end only: exactly the result of one call
+ *     over the whole stream.  A frame longer than a pass makes the pass double.
+ *   mgpu_pf_decode_device: data, msgs, signal_level, frame_of, frame_class, frame_off device pointers (data at any alignment; the
+ *     8-byte arrays 8-byte aligned); the counts are in host memory.  pass_bytes is ignored. */
+#define MGPU_PF_IN_MODEAC     1u   /* a Mode A/C record (accepted); the values up to _UNKNOWN are MGPU_RAW_*'s */
+#define MGPU_PF_IN_BAD        2u   /* rejected bad */
+#define MGPU_PF_IN_ACCEPT     3u   /* accepted */
+#define MGPU_PF_IN_COND       4u   /* mgpu_pf_parse_host only: accepted iff addr is in the filter */
+#define MGPU_PF_IN_UNKNOWN    5u   /* rejected unknown ICAO */
+#define MGPU_PF_IN_MODEAC_OFF 6u   /* Mode A/C with cfg.mode_ac off: no record, nothing counted */
+#define MGPU_PF_IN_TYPE       7u   /* a type nibble of 3 to 15: no record, nothing counted */
+/* what mgpu_pf_parse_host says of the step at an offset */
+#define MGPU_PF_STEP_END        0u   /* no DLE at or behind the offset: the loop ends, som stays */
+#define MGPU_PF_STEP_SKIP       1u   /* a DLE that starts no frame: next = its offset + 1 */
+#define MGPU_PF_STEP_OTHER      2u   /* a complete frame of another packet id: next = its end + 2 */
+#define MGPU_PF_STEP_FRAME      3u   /* a handler call: next = the frame's end + 2 */
+#define MGPU_PF_STEP_INCOMPLETE 4u   /* a start without an end: the call returns, som stays */
+struct mgpu_pf_in_counters {
+    uint64_t remote_received_modes, remote_received_modeac, remote_rejected_unknown_icao, remote_rejected_bad, remote_accepted[3];
+    uint64_t nskipped;                 /* complete frames with another packet id */
+    uint64_t past_end;                 /* handler calls whose decode read an index > nbytes */
+};
+struct mgpu_pf_in_frame {              /* 112 bytes */
+    struct mgpu_msg msg;               /* zero unless cls is MGPU_PF_IN_MODEAC, _ACCEPT or _COND */
+    double signal_level;
+    uint64_t next;                     /* the som the step leaves (END, INCOMPLETE: the offset itself) */
+    uint64_t frame_off;                /* OTHER, FRAME, INCOMPLETE: the start DLE */
+    uint32_t step;                     /* MGPU_PF_STEP_* */
+    uint32_t cls;                      /* step FRAME: MGPU_PF_IN_* (never _UNKNOWN); 0 otherwise */
+    uint32_t addr;                     /* the address the filter is asked about (_COND) or learns (adder) */
+    uint32_t adder;                    /* 1: a clean DF17 or a clean DF11 with IID 0 — icaoFilterAdd(addr) */
+    uint32_t past_end;                 /* 1: the decode read an index > nbytes */
+    uint32_t reserved;                 /* 0 */
+};
+struct mgpu_pf_in_args {
+    uint32_t size;                     /* sizeof(struct mgpu_pf_in_args) */
+    uint32_t look;                     /* bytes at data[nbytes ..) that are the stream's too (see above); 0: nbytes ends the stream */
+    const uint8_t *data;
+    uint64_t nbytes;
+    int64_t now_ms;
+    struct mgpu_msg *msgs;             /* msgs_cap entries: the accepted messages in stream order */
+    double *signal_level;              /* optional, msgs_cap entries: mm->signalLevel */
+    uint64_t *frame_of;                /* optional, msgs_cap entries: the handler call per message */
+    uint64_t msgs_cap;
+    uint8_t *frame_class;              /* optional, frames_cap entries: MGPU_PF_IN_* per handler call */
+    uint64_t *frame_off;               /* optional, frames_cap entries: the offset of each handler call's start DLE */
+    uint64_t frames_cap;
+    uint64_t *consumed, *nframes, *nmsgs;   /* host, out */
+    struct mgpu_pf_in_counters *counters;   /* host, out */
+    uint64_t pass_bytes;               /* host form: bytes staged per pass; 0 = the library's default */
+};
+int mgpu_pf_decode(mgpu_ctx *ctx, const struct mgpu_pf_in_args *args);          /* every array in host memory */
+int mgpu_pf_decode_device(mgpu_ctx *ctx, const struct mgpu_pf_in_args *args);   /* data and the per-message / per-call arrays device pointers */
+/* The step of readPlanefinder's loop with som at `offset` of a host buffer, by the same framer and parser (cfg: the raw input's;
+ * the CRC tables of cfg->nfix_crc built once per value): the som it leaves, the kind, and for a handler call its class, record,
+ * signal, the address asked about and the adder flag (MGPU_RAW_COND style).  Returns 1 for a handler call, 0 for any other step, or
+ * MGPU_E_INVAL (a NULL argument, offset >= nbytes).  Needs no context and no GPU. */
+int mgpu_pf_parse_host(const uint8_t *data, uint64_t nbytes, uint64_t offset, int64_t now_ms, const struct mgpu_raw_in_config *cfg, struct mgpu_pf_in_frame *out);
+
 #ifdef __cplusplus
 }
 #endif

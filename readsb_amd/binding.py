@@ -281,6 +281,29 @@ def beast_in_counters_dict(cn):
                 nreceiver_ids=int(cn.nreceiver_ids), ncommands=int(cn.ncommands))
 
 
+class PfInCounters(C.Structure):                                      # struct mgpu_pf_in_counters
+    _fields_ = [("remote_received_modes", C.c_uint64), ("remote_received_modeac", C.c_uint64), ("remote_rejected_unknown_icao", C.c_uint64),
+                ("remote_rejected_bad", C.c_uint64), ("remote_accepted", C.c_uint64 * 3), ("nskipped", C.c_uint64), ("past_end", C.c_uint64)]
+
+
+class PfInFrame(C.Structure):                                         # struct mgpu_pf_in_frame: 112 bytes
+    _fields_ = [("msg", C.c_uint8 * 64), ("signal_level", C.c_double), ("next", C.c_uint64), ("frame_off", C.c_uint64), ("step", C.c_uint32), ("cls", C.c_uint32),
+                ("addr", C.c_uint32), ("adder", C.c_uint32), ("past_end", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PfInArgs(C.Structure):                                          # struct mgpu_pf_in_args
+    _fields_ = [("size", C.c_uint32), ("look", C.c_uint32), ("data", C.c_void_p), ("nbytes", C.c_uint64), ("now_ms", C.c_int64), ("msgs", C.c_void_p),
+                ("signal_level", C.c_void_p), ("frame_of", C.c_void_p), ("msgs_cap", C.c_uint64), ("frame_class", C.c_void_p), ("frame_off", C.c_void_p),
+                ("frames_cap", C.c_uint64), ("consumed", C.POINTER(C.c_uint64)), ("nframes", C.POINTER(C.c_uint64)), ("nmsgs", C.POINTER(C.c_uint64)),
+                ("counters", C.POINTER(PfInCounters)), ("pass_bytes", C.c_uint64)]
+
+
+def pf_in_counters_dict(cn):
+    return dict(remote_received_modes=int(cn.remote_received_modes), remote_received_modeac=int(cn.remote_received_modeac),
+                remote_rejected_unknown_icao=int(cn.remote_rejected_unknown_icao), remote_rejected_bad=int(cn.remote_rejected_bad),
+                remote_accepted=[int(x) for x in cn.remote_accepted], nskipped=int(cn.nskipped), past_end=int(cn.past_end))
+
+
 class RawInFilter(C.Structure):                                       # struct mgpu_raw_in_filter
     _fields_ = [("gen_active", C.c_void_p), ("gen_inactive", C.c_void_p), ("n_active", C.c_uint64), ("n_inactive", C.c_uint64), ("occupied", C.c_uint32),
                 ("table_bits", C.c_uint32)]
@@ -508,6 +531,10 @@ def load_library():
     lib.mgpu_beast_decode_device.argtypes = [vp, C.POINTER(BeastInArgs)]
     lib.mgpu_beast_parse_host.argtypes = [vp, u64, u64, C.c_int64, C.POINTER(BeastInConfig), C.POINTER(BeastInFrame)]
     lib.mgpu_beast_decode_host.argtypes = [C.POINTER(BeastInArgs), C.POINTER(RawInConfig), C.POINTER(RawInFilter)]
+    lib.mgpu_pf_decode.argtypes = [vp, C.POINTER(PfInArgs)]
+    lib.mgpu_pf_decode_device.argtypes = [vp, C.POINTER(PfInArgs)]
+    lib.mgpu_pf_parse_host.argtypes = [vp, u64, u64, C.c_int64, C.POINTER(RawInConfig), C.POINTER(PfInFrame)]
+    lib.mgpu_pf_decode_host.argtypes = [C.POINTER(PfInArgs), C.POINTER(RawInConfig), C.POINTER(RawInFilter)]
     lib.mgpu_asterix_decode.argtypes = [vp, C.POINTER(AsterixInArgs)]
     lib.mgpu_asterix_decode_device.argtypes = [vp, C.POINTER(AsterixInArgs)]
     lib.mgpu_asterix_parse_host.argtypes = [C.POINTER(AsterixInArgs), u64, vp]
@@ -1201,6 +1228,24 @@ class Demodulator:
         return dict(msgs=msgs[:n].copy(), receiver_id=ids[:n].copy(), signal_level=signal[:n].copy(), frame_of=frame_of[:n].copy(), frame_class=cls[:nframes].copy(),
                     frame_off=off[:nframes].copy(), consumed=consumed, nframes=nframes, stop=int(stop.value), stop_off=stop_off, receiver_id_out=id_out,
                     counters=beast_in_counters_dict(cn))
+
+    def pf_decode(self, data, now_ms=0, pass_bytes=0):
+        """mgpu_pf_decode on a host byte string of the Planefinder binary feed (`--net-pfms-in-port`): one readPlanefinder with
+        decodePfMessage behind it — the accepted messages in stream order, the ICAO filter's answers as they stand at every frame; the
+        context's filter learns the stream's clean DF17 / DF11 addresses.
+        -> dict(msgs, signal_level, frame_of, frame_class, frame_off, consumed, nframes, counters)."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        most = buf.size // 4 + 1                            # a handler call needs 4 bytes (pf_in_format.h)
+        msgs, signal, frame_of = np.zeros(most, dtype=MSG_DTYPE), np.empty(most, dtype=np.float64), np.empty(most, dtype=np.uint64)
+        cls, off = np.zeros(most, dtype=np.uint8), np.zeros(most, dtype=np.uint64)
+        c = [C.c_uint64(0) for _ in range(3)]
+        cn = PfInCounters()
+        a = PfInArgs(C.sizeof(PfInArgs), 0, buf.ctypes.data if buf.size else None, buf.size, int(now_ms), msgs.ctypes.data, signal.ctypes.data, frame_of.ctypes.data, most,
+                     cls.ctypes.data, off.ctypes.data, most, C.pointer(c[0]), C.pointer(c[1]), C.pointer(c[2]), C.pointer(cn), int(pass_bytes))
+        self._chk(self.lib.mgpu_pf_decode(self.ctx, C.byref(a)), "mgpu_pf_decode")
+        consumed, nframes, n = (int(x.value) for x in c)
+        return dict(msgs=msgs[:n].copy(), signal_level=signal[:n].copy(), frame_of=frame_of[:n].copy(), frame_class=cls[:nframes].copy(), frame_off=off[:nframes].copy(),
+                    consumed=consumed, nframes=nframes, counters=pf_in_counters_dict(cn))
 
     def asterix_decode(self, data, source=1, now_ms=0, pass_bytes=0):
         """mgpu_asterix_decode on a host byte string of ASTERIX records (`--net-asterix-in-port`): one record per category-21 frame

@@ -47,6 +47,20 @@ struct BeastInBufs {
               total.as<unsigned long long>()};
         return MGPU_OK;
     }
+    // The Planefinder input's scratch (kernels.h PfInScratch) in the same buffers, by role — one call is live at a time: the tiles'
+    // event words where the entries are, their state bytes where the maps are; per lane a halfword; per tile four counts and two
+    // offsets; the totals (the candidate arrays are FilterPasses').
+    int reserve_pf(mgpu_ctx *c, uint64_t nbytes, PfInScratch *w) {
+        const size_t tiles = pf_in_tiles(nbytes) + 1;
+        if (int rc = entry.reserve(c, 5 * tiles * sizeof(uint32_t))) return rc;
+        if (int rc = maps.reserve(c, tiles)) return rc;
+        if (int rc = meta.reserve(c, tiles * kBlock * sizeof(uint16_t))) return rc;
+        if (int rc = blocks.reserve(c, 4 * tiles * sizeof(uint32_t))) return rc;
+        if (int rc = off.reserve(c, 2 * tiles * sizeof(uint64_t))) return rc;
+        if (int rc = total.reserve_exact(c, 16 * sizeof(unsigned long long))) return rc;
+        *w = {entry.as<uint32_t>(), maps.as<uint8_t>(), meta.as<uint16_t>(), blocks.as<uint32_t>(), off.as<unsigned long long>(), total.as<unsigned long long>()};
+        return MGPU_OK;
+    }
 };
 
 // The ASTERIX input's scratch (kernels.h AstInScratch): the tiles' and the groups' exit maps; the entries; three bitmaps per tile; per
@@ -102,7 +116,7 @@ struct Behind {
 
     // ---- the stream inputs ----
     LineScratch lines;
-    BeastInBufs beast_in;
+    BeastInBufs beast_in;                                    // (the Planefinder input frames in these too: reserve_pf)
     AstInBufs ast_in;
     FilterPasses filter;
     DevBuf d_uat_sig_table;                                  // PERSISTENT: the UAT input's table of signal bytes, uploaded on first use

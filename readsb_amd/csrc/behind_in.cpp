@@ -1,4 +1,4 @@
-// behind_in.cpp — behind the message list, the stream inputs: UAT, SBS, raw, beast and ASTERIX, each as a `_device` entry over a stream
+// behind_in.cpp — behind the message list, the stream inputs: UAT, SBS, raw, beast, Planefinder and ASTERIX, each as a `_device` entry over a stream
 // in HBM and a host form that stages the stream in passes (stream_passes.h); the filter passes the raw and the beast input share.
 // (The outputs over the list: behind_out.cpp.)
 #include "behind.h"
@@ -9,9 +9,10 @@
 #include "sbs_in_format.h"
 #include "raw_in_format.h"
 #include "beast_in_host.h"
+#include "pf_in_host.h"
 #include "asterix_in_format.h"
 
-constexpr uint64_t kLineDefaultPass = 64ull << 20;           // bytes the UAT, SBS, raw and beast host forms stage per pass, pass_bytes == 0
+constexpr uint64_t kLineDefaultPass = 64ull << 20;           // bytes the UAT, SBS, raw, beast and Planefinder host forms stage per pass, pass_bytes == 0
 constexpr uint64_t kAstInDefaultPass = 16ull << 20;          // ... and the ASTERIX host form
 
 // The counts of a UAT or SBS call, or of one pass of it (stream_passes.h), in the order of UatScratch's totals: lines, bytes consumed,
@@ -609,6 +610,135 @@ int mgpu_beast_decode(mgpu_ctx *c, const struct mgpu_beast_in_args *a) {
     if (prc != MGPU_OK) { c->resolver.filter().restore(before); return prc; }
     beast_in_report(a, all);
     return beast_in_finish(c, a, all, before, adds);
+}
+
+// ---- Planefinder input: readPlanefinder + decodePfMessage over a DLE-framed stream (pf_in_format.h, kernels/pf_in.inc) ----
+
+// a: data and the per-message / per-call arrays device pointers, the capacities what this stretch may store (frame_class and frame_off
+// indexed by this stretch's own handler calls); a.nbytes are framed, `look` bytes behind them are the stream's too; frame_base and
+// off_base are added to frame_of and frame_off.  The counts of this stretch; the filter moved on as in raw_decode_passes.
+static int pf_decode_passes(mgpu_ctx *c, const struct mgpu_pf_in_args &a, uint64_t look, uint64_t frame_base, uint64_t off_base, PfInCounts *n, std::vector<uint32_t> *adds) {
+    Behind &b = *c->behind;
+    const uint64_t cand_cap = pf_in_max_frames(a.nbytes);
+    PfInScratch w;
+    if (int rc = b.beast_in.reserve_pf(c, a.nbytes, &w)) return rc;
+    RawInParams p;
+    FilterGens r;
+    if (int rc = filter_passes_begin(c, cand_cap, p, r)) return rc;
+    p.text = a.data; p.nbytes = a.nbytes; p.now_ms = a.now_ms;
+    p.msgs = a.msgs; p.line_of = (unsigned long long *) a.frame_of; p.signal_level = a.signal_level; p.msgs_cap = a.msgs ? a.msgs_cap : 0;
+    p.line_class = a.frame_class; p.line_class_cap = a.frame_class ? a.frames_cap : 0; p.line_base = frame_base;
+    PfInParams q;
+    q.data = a.data; q.nbytes = a.nbytes; q.look = look; q.cfg = p.cfg;
+    q.frame_class = a.frame_class; q.frame_off = (unsigned long long *) a.frame_off; q.frames_cap = (a.frame_class || a.frame_off) ? a.frames_cap : 0; q.off_base = off_base;
+    launch_pf_in_front(q, p, w, c->stream_aux);
+    HIPCHK(c, hipGetLastError());
+    unsigned long long total[6];
+    HIPCHK(c, hipMemcpyAsync(total, w.total, sizeof total, hipMemcpyDeviceToHost, c->stream_aux));
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    unsigned long long misc[16];
+    int rc = MGPU_OK;
+    if (total[1] > cand_cap) { c->err = "pf decode: more candidates than the stream can hold"; rc = MGPU_E_OVERFLOW; }   // (cannot happen: pf_in_max_frames)
+    // (every handler call's class is stored, by k_pf_in_classify or by the filter passes: nothing to zero)
+    if (int rc2 = filter_passes_end(c, p, r, rc ? 0 : total[1], 0, misc, adds)) return rc2;
+    if (rc) return rc;
+    n->frames = total[0]; n->msgs = misc[10]; n->consumed = total[4];
+    n->cn[0] = misc[2] + misc[3] + misc[4] + misc[5] + misc[6];   // remote_received_modes: every Mode S frame that reached the decode
+    for (int k = 1; k < 7; ++k) n->cn[k] = misc[k];
+    n->cn[7] = total[2]; n->cn[8] = total[3];
+    return MGPU_OK;
+}
+
+static int pf_decode_dev(mgpu_ctx *c, const struct mgpu_pf_in_args &a, uint64_t look, uint64_t frame_base, uint64_t off_base, PfInCounts *n, std::vector<uint32_t> *adds) {
+    return filter_tables_after(c, pf_decode_passes(c, a, look, frame_base, off_base, n, adds));
+}
+
+static bool pf_in_args_ok(const struct mgpu_pf_in_args *a) {
+    if (!a || a->size < sizeof(struct mgpu_pf_in_args) || !a->consumed || !a->nframes || !a->nmsgs || !a->counters) return false;
+    if (a->nbytes + a->look >= (1ull << 32) || a->msgs_cap > UINT64_MAX / sizeof(mgpu_msg) || a->frames_cap > UINT64_MAX / sizeof(uint64_t)) return false;
+    if (a->now_ms < 0 || a->now_ms >= 253402300800000ll) return false;
+    if (a->nbytes && !a->data) return false;
+    if ((a->msgs_cap && !a->msgs) || (a->frames_cap && !a->frame_class && !a->frame_off)) return false;
+    return true;
+}
+
+static void pf_in_report(const struct mgpu_pf_in_args *a, const PfInCounts &n) {
+    *a->consumed = n.consumed; *a->nframes = n.frames; *a->nmsgs = n.msgs;
+    pf_in_counters_of(n, a->counters);
+}
+
+static int pf_in_finish(mgpu_ctx *c, const struct mgpu_pf_in_args *a, const PfInCounts &n, const IcaoFilter::Snapshot &before, const std::vector<uint32_t> &adds) {
+    const char *overflow = n.msgs > a->msgs_cap ? "pf decode: more messages than the arrays hold" :
+                           (a->frame_class || a->frame_off) && n.frames > a->frames_cap ? "pf decode: more handler calls than the frame arrays hold" : nullptr;
+    return filter_call_end(c, overflow, before, adds);
+}
+
+int mgpu_pf_decode_device(mgpu_ctx *c, const struct mgpu_pf_in_args *a) {
+    if (!c || !pf_in_args_ok(a)) return MGPU_E_INVAL;
+    if (((uintptr_t) a->msgs | (uintptr_t) a->frame_of | (uintptr_t) a->signal_level | (uintptr_t) a->frame_off) & 7u) return MGPU_E_INVAL;
+    PfInCounts n;
+    pf_in_report(a, n);
+    if (a->nbytes == 0) return MGPU_OK;
+    { const int rc = drain(c); if (rc != MGPU_OK) return rc; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    IcaoFilter::Snapshot before;
+    c->resolver.filter().snapshot(before);
+    std::vector<uint32_t> adds;
+    if (int rc = pf_decode_dev(c, *a, a->look, 0, 0, &n, &adds)) { c->resolver.filter().restore(before); return rc; }
+    pf_in_report(a, n);
+    return pf_in_finish(c, a, n, before, adds);
+}
+
+int mgpu_pf_decode(mgpu_ctx *c, const struct mgpu_pf_in_args *a) {
+    if (!c || !pf_in_args_ok(a)) return MGPU_E_INVAL;
+    PfInCounts all;
+    pf_in_report(a, all);
+    if (a->nbytes == 0) return MGPU_OK;
+    { const int rc = drain(c); if (rc != MGPU_OK) return rc; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    Behind &b = *c->behind;
+    IcaoFilter::Snapshot before;
+    c->resolver.filter().snapshot(before);
+    std::vector<uint32_t> adds;
+    const bool want_frames = a->frame_class || a->frame_off;
+    size_t adds_before = 0;
+    IcaoFilter::Snapshot pass_before;
+    const int prc = stream_passes(a->nbytes, a->pass_bytes ? a->pass_bytes : kLineDefaultPass, false, all,
+        [&](uint64_t at, uint64_t nb, bool, const PfInCounts &so_far, PfInCounts &n) -> int {
+            // a pass frames nb bytes; the lookahead and the handler's reads may take kPfInReach more, which decide every frame that starts
+            // inside the pass; what the caller's arrays still hold, and no more than nb bytes can give
+            const uint64_t look = pf_in_look(a->nbytes + a->look, at, nb);
+            const uint64_t msg_room = a->msgs_cap > so_far.msgs ? std::min<uint64_t>(a->msgs_cap - so_far.msgs, pf_in_max_frames(nb)) : 0;
+            const uint64_t frame_room = want_frames && a->frames_cap > so_far.frames ? std::min<uint64_t>(a->frames_cap - so_far.frames, pf_in_max_frames(nb)) : 0;
+            int rc;
+            if ((rc = b.d_stream.reserve(c, nb + look + 64)) || (rc = b.d_in_msgs.reserve(c, (msg_room + 1) * sizeof(mgpu_msg))) ||
+                (rc = b.d_index_of.reserve(c, (msg_room + 1) * sizeof(uint64_t))) || (rc = b.d_in_signal.reserve(c, (msg_room + 1) * sizeof(double))) ||
+                (rc = b.d_in_class.reserve(c, frame_room + 1)) || (rc = b.d_bin_frame_off.reserve(c, (frame_room + 1) * sizeof(uint64_t)))) return rc;
+            struct mgpu_pf_in_args d = *a;
+            d.data = b.d_stream.as<uint8_t>(); d.nbytes = nb;
+            d.msgs = b.d_in_msgs.as<mgpu_msg>(); d.msgs_cap = msg_room;
+            d.frame_of = a->frame_of ? b.d_index_of.as<uint64_t>() : nullptr;
+            d.signal_level = a->signal_level ? b.d_in_signal.as<double>() : nullptr;
+            d.frame_class = a->frame_class ? b.d_in_class.as<uint8_t>() : nullptr;
+            d.frame_off = a->frame_off ? b.d_bin_frame_off.as<uint64_t>() : nullptr;
+            d.frames_cap = frame_room;
+            HIPCHK(c, hipMemcpyAsync(b.d_stream.p, a->data + at, nb + look, hipMemcpyHostToDevice, c->stream_aux));
+            adds_before = adds.size();
+            c->resolver.filter().snapshot(pass_before);
+            if ((rc = pf_decode_dev(c, d, look, so_far.frames, at, &n, &adds))) return rc;
+            // (the pass stored below its rooms only: the copies stay inside the caller's arrays)
+            const uint64_t nmsg = std::min<uint64_t>(n.msgs, msg_room), nfr = std::min<uint64_t>(n.frames, frame_room);
+            if (nmsg) HIPCHK(c, hipMemcpy(a->msgs + so_far.msgs, d.msgs, nmsg * sizeof(mgpu_msg), hipMemcpyDeviceToHost));
+            if (nmsg && a->frame_of) HIPCHK(c, hipMemcpy(a->frame_of + so_far.msgs, d.frame_of, nmsg * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            if (nmsg && a->signal_level) HIPCHK(c, hipMemcpy(a->signal_level + so_far.msgs, d.signal_level, nmsg * sizeof(double), hipMemcpyDeviceToHost));
+            if (nfr && a->frame_class) HIPCHK(c, hipMemcpy(a->frame_class + so_far.frames, d.frame_class, nfr, hipMemcpyDeviceToHost));
+            if (nfr && a->frame_off) HIPCHK(c, hipMemcpy(a->frame_off + so_far.frames, d.frame_off, nfr * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            return MGPU_OK;
+        },
+        [&] { c->resolver.filter().restore(pass_before); adds.resize(adds_before); });
+    if (prc != MGPU_OK) { c->resolver.filter().restore(before); return prc; }
+    pf_in_report(a, all);
+    return pf_in_finish(c, a, all, before, adds);
 }
 
 // ---- ASTERIX input: readAsterix + decodeAsterixMessage over a length-chained stream (asterix_in_format.h, kernels/asterix_in.inc) ----

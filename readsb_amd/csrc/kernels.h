@@ -20,6 +20,7 @@
 #include "../../include/modes_gpu.h"   // struct mgpu_msg (the beast encoder reads it on the device)
 #include "raw_in_format.h"
 #include "beast_in_format.h"
+#include "pf_in_format.h"
 
 namespace mgpu {
 
@@ -388,6 +389,30 @@ struct BeastInScratch {
     unsigned long long *total;        // [9] see launch_beast_in_front
 };
 void launch_beast_in_front(const BeastInParams &a, const RawInParams &p, const BeastInScratch &w, hipStream_t s);
+// Planefinder input (kernels/pf_in.inc; readPlanefinder + decodePfMessage over a DLE-framed stream, pf_in_format.h): the UAT input's
+// tiles; the framer is a two-state automaton whose state at an offset is the kind of the last event in front of it, so the tiles need
+// one scan of their last events and no chain.  It ends in the raw input's candidate arrays and filter passes (RawInParams: a "line" is
+// a handler call)
+constexpr size_t pf_in_tiles(uint64_t nbytes) { return (size_t) ((nbytes + kUatTile - 1) / kUatTile); }
+struct PfInParams {
+    const uint8_t *data;              // any alignment
+    uint64_t nbytes;                  // what is framed
+    uint64_t look;                    // bytes behind them that are the stream's too: lookahead and the handler's reads (the host form's passes)
+    RawInConfig cfg;
+    uint8_t *frame_class;             // optional: the classes the filter does not decide; nothing at or beyond frames_cap is stored
+    unsigned long long *frame_off;    // optional
+    uint64_t frames_cap;
+    uint64_t off_base;                // added to every frame_off (the host form's passes)
+};
+struct PfInScratch {
+    uint32_t *ev;                     // [5 * tiles] per tile: see k_pf_in_events
+    uint8_t *in_frame;                // [tiles] the framer's state at the tile's first byte
+    uint16_t *meta;                   // [tiles * kBlock] per lane: handler calls | candidates << 8
+    uint32_t *blocks;                 // [4 * tiles] per tile: handler calls | candidates | frames of another packet id | reads past the end
+    unsigned long long *off;          // [2 * tiles] the exclusive prefix sums of the first two
+    unsigned long long *total;        // [6] see launch_pf_in_front
+};
+void launch_pf_in_front(const PfInParams &a, const RawInParams &p, const PfInScratch &w, hipStream_t s);
 // ASTERIX input (kernels/asterix_in.inc; readAsterix + decodeAsterixMessage over a length-chained stream, asterix_in_format.h)
 constexpr uint32_t kAstTile = 65536;          // bytes per tile: a length is below 65536, so a chain that enters tile t leaves it into tile t + 1
 constexpr uint32_t kAstGroup = 32;            // tiles whose exit maps are composed into one

@@ -20,6 +20,8 @@
 //                    mode_s.c:443-606, 766-779)
 //   k_beast_in_*     `--net-bi-port`: a beast binary stream to accepted messages with their receiver ids, readBeast's escape-and-resync
 //                    framing as composed tile maps, then the raw input's decode and filter passes (net_io.c:4737-5018, 3804-3961)
+//   k_pf_in_*        `--net-pfms-in-port`: a Planefinder DLE stream to accepted messages, readPlanefinder's framing as a scan of the
+//                    tiles' last events, then the raw input's decode and filter passes (net_io.c:4670-4735, 3995-4101)
 //   k_ast_in_*       `--net-asterix-in-port`: a length-chained stream of CAT021 records to aircraft records (net_io.c:4643-4659, 1922-2407)
 //
 // No MFMA anywhere: this is HBM-bound integer/byte streaming work.  All arithmetic on the
@@ -144,6 +146,7 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 #include "kernels/sbs_in.inc"
 #include "kernels/raw_in.inc"
 #include "kernels/beast_in.inc"
+#include "kernels/pf_in.inc"
 #include "kernels/asterix_in.inc"
 #include "kernels/fields.inc"
 #include "kernels/gate.inc"
