@@ -11,26 +11,20 @@
 
 namespace mgpu {
 
-// the counts of a call or of one pass of it
-struct BeastInCounts {
-    uint64_t frames = 0, consumed = 0, msgs = 0, id = 0, stop_off = 0;
-    uint32_t stop = MGPU_BEAST_STOP_END;
-    uint64_t cn[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};          // struct mgpu_beast_in_counters in its order
-    // for stream_passes (stream_passes.h, shared by mgpu_beast_decode over the device and the sequential walk with args->pass_bytes
-    // != 0): a stretch is cut at the last som it reached; the receiver id is carried, the tail rule left to the stretch that ends the
-    // stream; a stretch in which no som is reached (a frame or a run without 0x1a longer than it) is the one that is repeated
-    bool stopped() const { return stop != MGPU_BEAST_STOP_END; }
-    void add(const BeastInCounts &n) {
-        frames += n.frames; msgs += n.msgs; id = n.id; stop = n.stop; stop_off = consumed;
-        for (int k = 0; k < 10; ++k) cn[k] += n.cn[k];
-    }
-};
-
-inline void beast_in_counters_of(const BeastInCounts &n, struct mgpu_beast_in_counters *k) {
-    k->remote_received_modes = n.cn[0]; k->remote_received_modeac = n.cn[1]; k->remote_rejected_unknown_icao = n.cn[2]; k->remote_rejected_bad = n.cn[3];
-    for (int i = 0; i < 3; ++i) k->remote_accepted[i] = n.cn[4 + i];
+// A call as the stretch it is and its counts to the caller (raw_in_host.h: MsgInStretch, MsgInCounts; a unit is a handler call).
+// Between passes (stream_passes.h) the receiver id is carried and the tail rule left to the stretch that ends the stream.
+#pragma GCC visibility push(hidden)
+inline MsgInStretch beast_in_stretch(const struct mgpu_beast_in_args &a) {
+    return {a.data, a.nbytes, 0, a.now_ms, a.msgs, a.receiver_id, a.signal_level, a.frame_of, a.msgs_cap, a.frame_class, a.frame_off, a.frames_cap, 0, 0, true,
+            a.receiver_id_in, a.net_ingest};
+}
+inline void beast_in_report(const struct mgpu_beast_in_args &a, const MsgInCounts &n) {
+    *a.consumed = n.consumed; *a.nframes = n.units; *a.nmsgs = n.msgs; *a.stop = n.stop; *a.stop_off = n.stop_off; *a.receiver_id_out = n.id;
+    struct mgpu_beast_in_counters *k = a.counters;
+    msg_in_counters_of(n, k);
     k->remote_malformed_beast = n.cn[7]; k->nreceiver_ids = n.cn[8]; k->ncommands = n.cn[9];
 }
+#pragma GCC visibility pop
 
 // One readBeast over a HOST-memory buffer, step by step, against `filter` (icao_filter.h), which is moved on as the reference's would
 // be; the outputs as mgpu_beast_decode gives them (capacities as there: MGPU_E_OVERFLOW with what is needed and the filter as it was).

@@ -1,5 +1,5 @@
 // behind_in.cpp — behind the message list, the stream inputs: UAT, SBS, raw, beast, Planefinder and ASTERIX, each as a `_device` entry over a stream
-// in HBM and a host form that stages the stream in passes (stream_passes.h); the filter passes the raw and the beast input share.
+// in HBM and a host form that stages the stream in passes (stream_passes.h); the one host core of the three message inputs.
 // (The outputs over the list: behind_out.cpp.)
 #include "behind.h"
 
@@ -220,20 +220,13 @@ int mgpu_sbs_decode(mgpu_ctx *c, const struct mgpu_sbs_in_args *a) {
     return sbs_in_verdict(c, a, all);
 }
 
-// ---- Raw input: decodeHexMessage + the front of decodeModesMessage over AVR lines (raw_in_format.h, kernels/raw_in.inc) ----
+// ---- The message inputs: raw (AVR lines; raw_in_format.h, kernels/raw_in.inc), beast (a binary stream; beast_in_format.h,
+// kernels/beast_in.inc) and Planefinder (a DLE-framed stream; pf_in_format.h, kernels/pf_in.inc).  Each frames its stream with a front
+// of its own and ends in the same candidate arrays and filter passes, so a call is written once (msg_in_passes, msg_in_staged,
+// msg_in_call) over a MsgInStretch (raw_in_host.h), and a format states only what is its own (RawIn, BeastIn, PfIn). ----
 
-struct RawInCounts {
-    uint64_t lines = 0, consumed = 0, msgs = 0;
-    uint64_t cn[7] = {0, 0, 0, 0, 0, 0, 0};
-    bool stopped() const { return false; }                      // (for stream_passes, as LineCounts)
-    void add(const RawInCounts &n) {
-        lines += n.lines; msgs += n.msgs;
-        for (int k = 0; k < 7; ++k) cn[k] += n.cn[k];
-    }
-};
-
-// The filter passes' side of a call (launch_raw_in_resolve), shared with the beast input: the candidate arrays and the tables reserved,
-// the filter's generations scattered into their bitmaps, p's candidate, table and filter fields set.
+// The filter passes' side of a call (launch_raw_in_resolve): the candidate arrays and the tables reserved, the filter's generations
+// scattered into their bitmaps, p's candidate, table and filter fields set.
 struct FilterGens {
     uint32_t *d_members, *gen_active, *gen_inactive;
     uint32_t na, ni;
@@ -322,61 +315,8 @@ static int filter_tables_after(mgpu_ctx *c, int rc) {
     return rc;
 }
 
-// a: text, msgs, line_of, signal_level, line_class device pointers, the capacities what this text may store (line_class indexed by
-// this text's own lines).  The counts of this text; the context's filter moved on by the text's new adds, which are appended to
-// *adds (the caller publishes them to the pre-screen's bitmap, or puts the filter back).
-static int raw_decode_passes(mgpu_ctx *c, const struct mgpu_raw_in_args &a, uint64_t line_base, RawInCounts *n, std::vector<uint32_t> *adds) {
-    Behind &b = *c->behind;
-    const uint64_t cand_cap = raw_in_max_cands(a.nbytes);
-    UatScratch w;
-    if (int rc = b.lines.reserve(c, a.nbytes, &w)) return rc;
-    RawInParams p;
-    FilterGens r;
-    if (int rc = filter_passes_begin(c, cand_cap, p, r)) return rc;
-    p.text = a.text; p.nbytes = a.nbytes; p.now_ms = a.now_ms;
-    p.msgs = a.msgs; p.line_of = (unsigned long long *) a.line_of; p.signal_level = a.signal_level; p.msgs_cap = a.msgs ? a.msgs_cap : 0;
-    p.line_class = a.line_class; p.line_class_cap = a.line_class ? a.line_class_cap : 0; p.line_base = line_base;
-    launch_raw_in_front(p, w, c->stream_aux);
-    HIPCHK(c, hipGetLastError());
-    unsigned long long total[3] = {0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(total, w.total, sizeof total, hipMemcpyDeviceToHost, c->stream_aux));
-    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
-    unsigned long long misc[16];
-    int rc = MGPU_OK;
-    const size_t ncls = p.line_class ? (size_t) std::min<uint64_t>(total[0], p.line_class_cap) : 0;   // "not a frame" is 0: only candidates store a class
-    if (total[2] > cand_cap) { c->err = "raw decode: more candidates than the text can hold"; rc = MGPU_E_OVERFLOW; }   // (cannot happen: raw_in_max_cands)
-    if (int rc2 = filter_passes_end(c, p, r, rc ? 0 : total[2], rc ? 0 : ncls, misc, adds)) return rc2;
-    if (rc) return rc;
-    n->lines = total[0]; n->consumed = total[1]; n->msgs = misc[10];
-    for (int k = 1; k < 7; ++k) n->cn[k] = misc[k];
-    n->cn[0] = misc[2] + misc[3] + misc[4] + misc[5] + misc[6];   // remote_received_modes: every Mode S line that reached the decode
-    return MGPU_OK;
-}
-
-static int raw_decode_dev(mgpu_ctx *c, const struct mgpu_raw_in_args &a, uint64_t line_base, RawInCounts *n, std::vector<uint32_t> *adds) {
-    return filter_tables_after(c, raw_decode_passes(c, a, line_base, n, adds));
-}
-
-static bool raw_in_args_ok(const struct mgpu_raw_in_args *a) {
-    if (!a || a->size < sizeof(struct mgpu_raw_in_args) || !a->consumed || !a->nlines || !a->nmsgs || !a->counters) return false;
-    if (a->nbytes >= (1ull << 32) || a->msgs_cap > UINT64_MAX / sizeof(mgpu_msg)) return false;
-    if (a->now_ms < 0 || a->now_ms >= 253402300800000ll) return false;
-    if (a->nbytes && !a->text) return false;
-    if ((a->msgs_cap && !a->msgs) || (a->line_class_cap && !a->line_class)) return false;
-    return true;
-}
-
-static void raw_in_report(const struct mgpu_raw_in_args *a, const RawInCounts &n) {
-    *a->consumed = n.consumed;
-    *a->nlines = n.lines;
-    *a->nmsgs = n.msgs;
-    struct mgpu_raw_in_counters &k = *a->counters;
-    k.remote_received_modes = n.cn[0]; k.remote_received_modeac = n.cn[1]; k.remote_rejected_unknown_icao = n.cn[2]; k.remote_rejected_bad = n.cn[3];
-    for (int i = 0; i < 3; ++i) k.remote_accepted[i] = n.cn[4 + i];
-}
-
 // the pre-screen learns the addresses a call added to the filter, as mgpu_filter_add teaches it one (nothing is in flight behind the
-// drain); the raw input's and the beast input's
+// drain)
 static int filter_publish_adds(mgpu_ctx *c, const std::vector<uint32_t> &adds) {
     if (adds.empty()) return MGPU_OK;
     Behind &b = *c->behind;
@@ -388,358 +328,245 @@ static int filter_publish_adds(mgpu_ctx *c, const std::vector<uint32_t> &adds) {
     return MGPU_OK;
 }
 
-// the end of a call (overflow: its text, or null): on overflow the filter goes back to where it stood; otherwise the pre-screen learns
-// the new addresses
-static int filter_call_end(mgpu_ctx *c, const char *overflow, const IcaoFilter::Snapshot &before, const std::vector<uint32_t> &adds) {
-    if (!overflow) return filter_publish_adds(c, adds);
-    c->resolver.filter().restore(before);
-    c->err = overflow;
+}  // extern "C"
+
+namespace {
+
+// What a format states of its own:
+//   Args, stretch(), report(): its public struct, onto a MsgInStretch and back from the counts (raw_in_host.h and its like);
+//   args_ok(), aligned(): its MGPU_E_INVAL conditions, the latter the `_device` entry's;
+//   max_cands(nb), max_units(nb): what nb bytes can give at the most; look(a, at, nb): what a pass stages behind its nb bytes;
+//   Scratch, reserve(), front(): the scratch of its front and the launch (s: the stretch; p: the filter passes' side filled);
+//   ntotal, cand_total: how many totals the front leaves, and which of them counts the candidates; total[0] counts the units;
+//   counts(): what the totals say beyond the units, the messages and the seven counters all three share;
+//   zero_class: only candidates store a class, so the array is zeroed first; tail_pass: stream_passes.h;
+//   has_ids, has_off: it has receiver ids, unit offsets (the staging buffers a pass reserves);
+//   overflow[]: its texts for more candidates than max_cands (cannot happen), more messages, more units than the arrays hold.
+struct RawIn {
+    using Args = struct mgpu_raw_in_args;
+    using Scratch = UatScratch;
+    static constexpr bool zero_class = true, tail_pass = true, has_ids = false, has_off = false;
+    static constexpr int ntotal = 3, cand_total = 2;
+    static constexpr const char *overflow[3] = {"raw decode: more candidates than the text can hold", "raw decode: more messages than the array holds",
+                                                "raw decode: more lines than line_class holds"};
+    static MsgInStretch stretch(const Args &a) { return raw_in_stretch(a); }
+    static void report(const Args &a, const MsgInCounts &n) { raw_in_report(a, n); }
+    static bool args_ok(const Args *a) {
+        if (!a || a->size < sizeof(Args) || !a->consumed || !a->nlines || !a->nmsgs || !a->counters) return false;
+        if (a->nbytes >= (1ull << 32) || a->msgs_cap > UINT64_MAX / sizeof(mgpu_msg)) return false;
+        if (a->now_ms < 0 || a->now_ms >= 253402300800000ll) return false;
+        if (a->nbytes && !a->text) return false;
+        return !((a->msgs_cap && !a->msgs) || (a->line_class_cap && !a->line_class));
+    }
+    static bool aligned(const Args &a) { return !(((uintptr_t) a.msgs | (uintptr_t) a.line_of | (uintptr_t) a.signal_level) & 7u); }
+    static uint64_t max_cands(uint64_t nb) { return raw_in_max_cands(nb); }
+    static uint64_t max_units(uint64_t nb) { return nb; }
+    static uint64_t look(const MsgInStretch &, uint64_t, uint64_t) { return 0; }
+    static int reserve(mgpu_ctx *c, uint64_t nb, Scratch *w) { return c->behind->lines.reserve(c, nb, w); }
+    static void front(mgpu_ctx *c, const MsgInStretch &, RawInParams &p, const Scratch &w) { launch_raw_in_front(p, w, c->stream_aux); }
+    static void counts(const MsgInStretch &, const unsigned long long *total, MsgInCounts *n) { n->consumed = total[1]; }
+};
+
+struct BeastIn {
+    using Args = struct mgpu_beast_in_args;
+    using Scratch = BeastInScratch;
+    // (every handler call's class is stored, by k_beast_in_classify or by the filter passes: nothing to zero)
+    static constexpr bool zero_class = false, tail_pass = false, has_ids = true, has_off = true;
+    static constexpr int ntotal = 9, cand_total = 1;
+    static constexpr const char *overflow[3] = {"beast decode: more candidates than the stream can hold", "beast decode: more messages than the arrays hold",
+                                                "beast decode: more handler calls than the frame arrays hold"};
+    static MsgInStretch stretch(const Args &a) { return beast_in_stretch(a); }
+    static void report(const Args &a, const MsgInCounts &n) { beast_in_report(a, n); }
+    static bool args_ok(const Args *a) {
+        if (!a || a->size < sizeof(Args) || !a->consumed || !a->nframes || !a->nmsgs || !a->stop || !a->stop_off || !a->receiver_id_out || !a->counters) return false;
+        if (a->nbytes >= (1ull << 32) || a->msgs_cap > UINT64_MAX / sizeof(mgpu_msg) || a->frames_cap > UINT64_MAX / sizeof(uint64_t)) return false;
+        if (a->now_ms < 0 || a->now_ms >= 253402300800000ll) return false;
+        if (a->nbytes && !a->data) return false;
+        return !((a->msgs_cap && (!a->msgs || !a->receiver_id)) || (a->frames_cap && !a->frame_class && !a->frame_off));
+    }
+    static bool aligned(const Args &a) {
+        return !(((uintptr_t) a.msgs | (uintptr_t) a.receiver_id | (uintptr_t) a.frame_of | (uintptr_t) a.signal_level | (uintptr_t) a.frame_off) & 7u);
+    }
+    static uint64_t max_cands(uint64_t nb) { return beast_in_max_msgs(nb); }
+    static uint64_t max_units(uint64_t nb) { return beast_in_max_frames(nb); }
+    static uint64_t look(const MsgInStretch &, uint64_t, uint64_t) { return 0; }
+    static int reserve(mgpu_ctx *c, uint64_t nb, Scratch *w) { return c->behind->beast_in.reserve(c, nb, w); }
+    static void front(mgpu_ctx *c, const MsgInStretch &s, RawInParams &p, const Scratch &w) {
+        p.cand_id = c->behind->beast_in.cand_id.as<unsigned long long>(); p.receiver_id = (unsigned long long *) s.ids;
+        BeastInParams q;
+        q.data = s.data; q.nbytes = s.nbytes; q.net_ingest = s.net_ingest ? 1u : 0u; q.cfg = p.cfg; q.receiver_id_in = s.receiver_id_in;
+        q.cand_id = c->behind->beast_in.cand_id.as<unsigned long long>();
+        q.frame_class = s.unit_class; q.frame_off = (unsigned long long *) s.unit_off; q.frames_cap = (s.unit_class || s.unit_off) ? s.units_cap : 0; q.off_base = s.off_base;
+        launch_beast_in_front(q, p, w, c->stream_aux);
+    }
+    static void counts(const MsgInStretch &s, const unsigned long long *total, MsgInCounts *n) {
+        n->id = total[8];
+        uint64_t garbage = total[2];
+        if (total[6] != ~0ull) {
+            const uint64_t at = total[6] >> 8, delta = (total[6] >> 3) & 31u;
+            n->stop = (total[6] & 7u) == BEAST_IN_STOP_SYNTH ? MGPU_BEAST_STOP_SYNTH : MGPU_BEAST_STOP_UUID;
+            n->consumed = at + delta;
+        } else {
+            n->consumed = total[7];
+            if (s.final && s.nbytes - n->consumed > kBeastInTail) {   // net_io.c:5010-5015
+                garbage += s.nbytes - n->consumed;
+                n->consumed = s.nbytes;
+            }
+        }
+        n->stop_off = n->consumed;
+        n->cn[1] += total[5];                                     // remote_received_modeac: the records, and the frames dropped with mode_ac off
+        n->cn[7] = garbage; n->cn[8] = total[4]; n->cn[9] = total[3];
+    }
+};
+
+struct PfIn {
+    using Args = struct mgpu_pf_in_args;
+    using Scratch = PfInScratch;
+    // (every handler call's class is stored, by k_pf_in_classify or by the filter passes: nothing to zero)
+    static constexpr bool zero_class = false, tail_pass = false, has_ids = false, has_off = true;
+    static constexpr int ntotal = 6, cand_total = 1;
+    static constexpr const char *overflow[3] = {"pf decode: more candidates than the stream can hold", "pf decode: more messages than the arrays hold",
+                                                "pf decode: more handler calls than the frame arrays hold"};
+    static MsgInStretch stretch(const Args &a) { return pf_in_stretch(a); }
+    static void report(const Args &a, const MsgInCounts &n) { pf_in_report(a, n); }
+    static bool args_ok(const Args *a) {
+        if (!a || a->size < sizeof(Args) || !a->consumed || !a->nframes || !a->nmsgs || !a->counters) return false;
+        if (a->nbytes + a->look >= (1ull << 32) || a->msgs_cap > UINT64_MAX / sizeof(mgpu_msg) || a->frames_cap > UINT64_MAX / sizeof(uint64_t)) return false;
+        if (a->now_ms < 0 || a->now_ms >= 253402300800000ll) return false;
+        if (a->nbytes && !a->data) return false;
+        return !((a->msgs_cap && !a->msgs) || (a->frames_cap && !a->frame_class && !a->frame_off));
+    }
+    static bool aligned(const Args &a) { return !(((uintptr_t) a.msgs | (uintptr_t) a.frame_of | (uintptr_t) a.signal_level | (uintptr_t) a.frame_off) & 7u); }
+    static uint64_t max_cands(uint64_t nb) { return pf_in_max_frames(nb); }
+    static uint64_t max_units(uint64_t nb) { return pf_in_max_frames(nb); }
+    // a pass frames nb bytes; the lookahead and the handler's reads may take kPfInReach more, which decide every frame that starts inside it
+    static uint64_t look(const MsgInStretch &a, uint64_t at, uint64_t nb) { return pf_in_look(a.nbytes + a.look, at, nb); }
+    static int reserve(mgpu_ctx *c, uint64_t nb, Scratch *w) { return c->behind->beast_in.reserve_pf(c, nb, w); }
+    static void front(mgpu_ctx *c, const MsgInStretch &s, RawInParams &p, const Scratch &w) {
+        PfInParams q;
+        q.data = s.data; q.nbytes = s.nbytes; q.look = s.look; q.cfg = p.cfg;
+        q.frame_class = s.unit_class; q.frame_off = (unsigned long long *) s.unit_off; q.frames_cap = (s.unit_class || s.unit_off) ? s.units_cap : 0; q.off_base = s.off_base;
+        launch_pf_in_front(q, p, w, c->stream_aux);
+    }
+    static void counts(const MsgInStretch &, const unsigned long long *total, MsgInCounts *n) {
+        n->consumed = total[4];
+        n->cn[7] = total[2]; n->cn[8] = total[3];
+    }
+};
+
+// The passes over one stretch on the device.  s: data and the arrays device pointers, the capacities what this stretch may store (the
+// per-unit arrays indexed by this stretch's own units).  The counts of this stretch; the context's filter moved on by the stretch's
+// new adds, which are appended to *adds (the caller publishes them to the pre-screen's bitmap, or puts the filter back).
+template <class F>
+static int msg_in_passes(mgpu_ctx *c, const MsgInStretch &s, MsgInCounts *n, std::vector<uint32_t> *adds) {
+    const uint64_t cand_cap = F::max_cands(s.nbytes);
+    typename F::Scratch w;
+    if (int rc = F::reserve(c, s.nbytes, &w)) return rc;
+    RawInParams p;
+    FilterGens r;
+    if (int rc = filter_passes_begin(c, cand_cap, p, r)) return rc;
+    p.text = s.data; p.nbytes = s.nbytes; p.now_ms = s.now_ms;
+    p.msgs = s.msgs; p.line_of = (unsigned long long *) s.index_of; p.signal_level = s.signal; p.msgs_cap = s.msgs ? s.msgs_cap : 0;
+    p.line_class = s.unit_class; p.line_class_cap = s.unit_class ? s.units_cap : 0; p.line_base = s.unit_base;
+    F::front(c, s, p, w);
+    HIPCHK(c, hipGetLastError());
+    unsigned long long total[F::ntotal] = {};
+    HIPCHK(c, hipMemcpyAsync(total, w.total, sizeof total, hipMemcpyDeviceToHost, c->stream_aux));
+    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
+    unsigned long long misc[16];
+    int rc = MGPU_OK;
+    const size_t ncls = F::zero_class && p.line_class ? (size_t) std::min<uint64_t>(total[0], p.line_class_cap) : 0;   // "not a frame" is 0
+    if (total[F::cand_total] > cand_cap) { c->err = F::overflow[0]; rc = MGPU_E_OVERFLOW; }
+    if (int rc2 = filter_passes_end(c, p, r, rc ? 0 : total[F::cand_total], rc ? 0 : ncls, misc, adds)) return rc2;
+    if (rc) return rc;
+    n->units = total[0]; n->msgs = misc[10];
+    n->cn[0] = misc[2] + misc[3] + misc[4] + misc[5] + misc[6];   // remote_received_modes: every Mode S unit that reached the decode
+    for (int k = 1; k < 7; ++k) n->cn[k] = misc[k];
+    F::counts(s, total, n);
+    return MGPU_OK;
+}
+
+// The host form: a's arrays in host memory, the stream staged in passes (stream_passes.h) whose results go through the staging
+// buffers; the filter, the receiver id and the remainder carried from pass to pass.  The counts of the stream in *all.
+template <class F>
+static int msg_in_staged(mgpu_ctx *c, const MsgInStretch &a, uint64_t pass_bytes, MsgInCounts *all, std::vector<uint32_t> *adds) {
+    Behind &b = *c->behind;
+    IcaoFilter &flt = c->resolver.filter();
+    IcaoFilter::Snapshot pass_before;
+    size_t adds_before = 0;
+    const bool want_units = a.unit_class || a.unit_off;
+    return stream_passes(a.nbytes, pass_bytes ? pass_bytes : kLineDefaultPass, F::tail_pass, *all,
+        [&](uint64_t at, uint64_t nb, bool final, const MsgInCounts &so_far, MsgInCounts &n) -> int {
+            // what this pass may write: what the caller's arrays still hold, and no more than nb bytes can give
+            const uint64_t look = F::look(a, at, nb);
+            const uint64_t msg_room = a.msgs_cap > so_far.msgs ? std::min<uint64_t>(a.msgs_cap - so_far.msgs, F::max_cands(nb)) : 0;
+            const uint64_t unit_room = want_units && a.units_cap > so_far.units ? std::min<uint64_t>(a.units_cap - so_far.units, F::max_units(nb)) : 0;
+            int rc;
+            if ((rc = b.d_stream.reserve(c, nb + look + 64)) || (rc = b.d_in_msgs.reserve(c, (msg_room + 1) * sizeof(mgpu_msg))) ||
+                (F::has_ids && (rc = b.d_bin_ids.reserve(c, (msg_room + 1) * sizeof(uint64_t)))) || (rc = b.d_index_of.reserve(c, (msg_room + 1) * sizeof(uint64_t))) ||
+                (rc = b.d_in_signal.reserve(c, (msg_room + 1) * sizeof(double))) || (rc = b.d_in_class.reserve(c, unit_room + 1)) ||
+                (F::has_off && (rc = b.d_bin_frame_off.reserve(c, (unit_room + 1) * sizeof(uint64_t))))) return rc;
+            MsgInStretch d = a;
+            d.data = b.d_stream.as<uint8_t>(); d.nbytes = nb; d.look = look; d.final = final; d.receiver_id_in = so_far.id;
+            d.msgs = b.d_in_msgs.as<mgpu_msg>(); d.ids = F::has_ids ? b.d_bin_ids.as<uint64_t>() : nullptr; d.msgs_cap = msg_room;
+            d.index_of = a.index_of ? b.d_index_of.as<uint64_t>() : nullptr;
+            d.signal = a.signal ? b.d_in_signal.as<double>() : nullptr;
+            d.unit_class = a.unit_class ? b.d_in_class.as<uint8_t>() : nullptr;
+            d.unit_off = a.unit_off ? b.d_bin_frame_off.as<uint64_t>() : nullptr;
+            d.units_cap = unit_room; d.unit_base = so_far.units; d.off_base = at;
+            HIPCHK(c, hipMemcpyAsync(b.d_stream.p, a.data + at, nb + look, hipMemcpyHostToDevice, c->stream_aux));
+            adds_before = adds->size();
+            flt.snapshot(pass_before);
+            if ((rc = filter_tables_after(c, msg_in_passes<F>(c, d, &n, adds)))) return rc;
+            // (the pass stored below its rooms only: the copies stay inside the caller's arrays)
+            const uint64_t nmsg = std::min<uint64_t>(n.msgs, msg_room), nunit = std::min<uint64_t>(n.units, unit_room);
+            if (nmsg) HIPCHK(c, hipMemcpy(a.msgs + so_far.msgs, d.msgs, nmsg * sizeof(mgpu_msg), hipMemcpyDeviceToHost));
+            if (nmsg && a.ids) HIPCHK(c, hipMemcpy(a.ids + so_far.msgs, d.ids, nmsg * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            if (nmsg && a.index_of) HIPCHK(c, hipMemcpy(a.index_of + so_far.msgs, d.index_of, nmsg * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            if (nmsg && a.signal) HIPCHK(c, hipMemcpy(a.signal + so_far.msgs, d.signal, nmsg * sizeof(double), hipMemcpyDeviceToHost));
+            if (nunit && a.unit_class) HIPCHK(c, hipMemcpy(a.unit_class + so_far.units, d.unit_class, nunit, hipMemcpyDeviceToHost));
+            if (nunit && a.unit_off) HIPCHK(c, hipMemcpy(a.unit_off + so_far.units, d.unit_off, nunit * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            return MGPU_OK;
+        },
+        [&] { flt.restore(pass_before); adds->resize(adds_before); });   // a larger pass, from the same filter
+}
+
+// A call of either form (staged: the host form).  An empty stream is answered before anything is drained.  Around the passes the
+// filter's one snapshot: an error or an overflow puts the filter back where it stood and teaches the pre-screen nothing; otherwise
+// the pre-screen learns the new addresses.
+template <class F>
+static int msg_in_call(mgpu_ctx *c, const typename F::Args *a, bool staged) {
+    if (!c || !F::args_ok(a) || (!staged && !F::aligned(*a))) return MGPU_E_INVAL;
+    const MsgInStretch s = F::stretch(*a);
+    MsgInCounts n;
+    n.id = s.receiver_id_in;
+    F::report(*a, n);
+    if (s.nbytes == 0) return MGPU_OK;
+    { const int rc = drain(c); if (rc != MGPU_OK) return rc; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    IcaoFilter &flt = c->resolver.filter();
+    IcaoFilter::Snapshot before;
+    flt.snapshot(before);
+    std::vector<uint32_t> adds;
+    if (int rc = staged ? msg_in_staged<F>(c, s, a->pass_bytes, &n, &adds) : filter_tables_after(c, msg_in_passes<F>(c, s, &n, &adds))) { flt.restore(before); return rc; }
+    F::report(*a, n);
+    const int over = msg_in_overflow(s, n);
+    if (!over) return filter_publish_adds(c, adds);
+    flt.restore(before);
+    c->err = F::overflow[over];
     return MGPU_E_OVERFLOW;
 }
 
-static int raw_in_finish(mgpu_ctx *c, const struct mgpu_raw_in_args *a, const RawInCounts &n, const IcaoFilter::Snapshot &before, const std::vector<uint32_t> &adds) {
-    const char *overflow = n.msgs > a->msgs_cap ? "raw decode: more messages than the array holds" :
-                           a->line_class && n.lines > a->line_class_cap ? "raw decode: more lines than line_class holds" : nullptr;
-    return filter_call_end(c, overflow, before, adds);
-}
+}  // namespace
 
-int mgpu_raw_decode_device(mgpu_ctx *c, const struct mgpu_raw_in_args *a) {
-    if (!c || !raw_in_args_ok(a)) return MGPU_E_INVAL;
-    if (((uintptr_t) a->msgs | (uintptr_t) a->line_of | (uintptr_t) a->signal_level) & 7u) return MGPU_E_INVAL;
-    RawInCounts n;
-    raw_in_report(a, n);
-    if (a->nbytes == 0) return MGPU_OK;
-    { const int rc = drain(c); if (rc != MGPU_OK) return rc; }
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    IcaoFilter::Snapshot before;
-    c->resolver.filter().snapshot(before);
-    std::vector<uint32_t> adds;
-    if (int rc = raw_decode_dev(c, *a, 0, &n, &adds)) { c->resolver.filter().restore(before); return rc; }
-    raw_in_report(a, n);
-    return raw_in_finish(c, a, n, before, adds);
-}
+extern "C" {
 
-int mgpu_raw_decode(mgpu_ctx *c, const struct mgpu_raw_in_args *a) {
-    if (!c || !raw_in_args_ok(a)) return MGPU_E_INVAL;
-    RawInCounts all;
-    raw_in_report(a, all);
-    if (a->nbytes == 0) return MGPU_OK;
-    { const int rc = drain(c); if (rc != MGPU_OK) return rc; }
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    Behind &b = *c->behind;
-    IcaoFilter::Snapshot before, pass_before;
-    c->resolver.filter().snapshot(before);
-    std::vector<uint32_t> adds;
-    size_t adds_before = 0;
-    const int prc = stream_passes(a->nbytes, a->pass_bytes ? a->pass_bytes : kLineDefaultPass, true, all,
-        [&](uint64_t at, uint64_t nb, bool final, const RawInCounts &so_far, RawInCounts &n) -> int {
-            // what this pass may write: what the caller's arrays still hold, and no more than nb bytes of text can give
-            const uint64_t msg_room = a->msgs_cap > so_far.msgs ? std::min<uint64_t>(a->msgs_cap - so_far.msgs, raw_in_max_cands(nb)) : 0;
-            const uint64_t cls_room = a->line_class_cap > so_far.lines ? std::min<uint64_t>(a->line_class_cap - so_far.lines, nb) : 0;
-            int rc;
-            if ((rc = b.d_stream.reserve(c, nb + 64)) || (rc = b.d_in_msgs.reserve(c, (msg_room + 1) * sizeof(mgpu_msg))) ||
-                (rc = b.d_index_of.reserve(c, (msg_room + 1) * sizeof(uint64_t))) || (rc = b.d_in_signal.reserve(c, (msg_room + 1) * sizeof(double))) ||
-                (rc = b.d_in_class.reserve(c, cls_room + 1))) return rc;
-            struct mgpu_raw_in_args d = *a;
-            d.text = b.d_stream.as<uint8_t>(); d.nbytes = nb;
-            d.msgs = b.d_in_msgs.as<mgpu_msg>(); d.msgs_cap = msg_room;
-            d.line_of = a->line_of ? b.d_index_of.as<uint64_t>() : nullptr;
-            d.signal_level = a->signal_level ? b.d_in_signal.as<double>() : nullptr;
-            d.line_class = a->line_class ? b.d_in_class.as<uint8_t>() : nullptr; d.line_class_cap = cls_room;
-            HIPCHK(c, hipMemcpyAsync(b.d_stream.p, a->text + at, nb, hipMemcpyHostToDevice, c->stream_aux));
-            adds_before = adds.size();
-            if (!final) c->resolver.filter().snapshot(pass_before);   // (only such a pass can be repeated)
-            if ((rc = raw_decode_dev(c, d, so_far.lines, &n, &adds))) return rc;
-            // (the pass stored below its rooms only: the copies stay inside the caller's arrays)
-            const uint64_t nmsg = std::min<uint64_t>(n.msgs, msg_room), ncls = std::min<uint64_t>(n.lines, cls_room);
-            if (nmsg) HIPCHK(c, hipMemcpy(a->msgs + so_far.msgs, d.msgs, nmsg * sizeof(mgpu_msg), hipMemcpyDeviceToHost));
-            if (nmsg && a->line_of) HIPCHK(c, hipMemcpy(a->line_of + so_far.msgs, d.line_of, nmsg * sizeof(uint64_t), hipMemcpyDeviceToHost));
-            if (nmsg && a->signal_level) HIPCHK(c, hipMemcpy(a->signal_level + so_far.msgs, d.signal_level, nmsg * sizeof(double), hipMemcpyDeviceToHost));
-            if (ncls && a->line_class) HIPCHK(c, hipMemcpy(a->line_class + so_far.lines, d.line_class, ncls, hipMemcpyDeviceToHost));
-            return MGPU_OK;
-        },
-        [&] { c->resolver.filter().restore(pass_before); adds.resize(adds_before); });   // a larger pass, from the same filter
-    if (prc != MGPU_OK) { c->resolver.filter().restore(before); return prc; }
-    raw_in_report(a, all);
-    return raw_in_finish(c, a, all, before, adds);
-}
-
-// ---- Beast input: readBeast + decodeBinMessage over a binary stream (beast_in_format.h, kernels/beast_in.inc) ----
-
-// a: data and the per-message / per-call arrays device pointers, the capacities what this stretch may store (frame_class and frame_off
-// indexed by this stretch's own handler calls); frame_base and off_base are added to frame_of and frame_off.  final: the tail rule
-// applies.  The counts of this stretch; the filter moved on as in raw_decode_passes.
-static int beast_decode_passes(mgpu_ctx *c, const struct mgpu_beast_in_args &a, uint64_t frame_base, uint64_t off_base, bool final, BeastInCounts *n,
-                               std::vector<uint32_t> *adds) {
-    Behind &b = *c->behind;
-    const uint64_t cand_cap = beast_in_max_msgs(a.nbytes);
-    BeastInScratch w;
-    if (int rc = b.beast_in.reserve(c, a.nbytes, &w)) return rc;
-    RawInParams p;
-    FilterGens r;
-    if (int rc = filter_passes_begin(c, cand_cap, p, r)) return rc;
-    p.text = a.data; p.nbytes = a.nbytes; p.now_ms = a.now_ms;
-    p.msgs = a.msgs; p.line_of = (unsigned long long *) a.frame_of; p.signal_level = a.signal_level; p.msgs_cap = a.msgs ? a.msgs_cap : 0;
-    p.line_class = a.frame_class; p.line_class_cap = a.frame_class ? a.frames_cap : 0; p.line_base = frame_base;
-    p.cand_id = b.beast_in.cand_id.as<unsigned long long>(); p.receiver_id = (unsigned long long *) a.receiver_id;
-    BeastInParams q;
-    q.data = a.data; q.nbytes = a.nbytes; q.net_ingest = a.net_ingest ? 1u : 0u; q.cfg = p.cfg; q.receiver_id_in = a.receiver_id_in;
-    q.cand_id = b.beast_in.cand_id.as<unsigned long long>();
-    q.frame_class = a.frame_class; q.frame_off = (unsigned long long *) a.frame_off; q.frames_cap = (a.frame_class || a.frame_off) ? a.frames_cap : 0; q.off_base = off_base;
-    launch_beast_in_front(q, p, w, c->stream_aux);
-    HIPCHK(c, hipGetLastError());
-    unsigned long long total[9];
-    HIPCHK(c, hipMemcpyAsync(total, w.total, sizeof total, hipMemcpyDeviceToHost, c->stream_aux));
-    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
-    unsigned long long misc[16];
-    int rc = MGPU_OK;
-    if (total[1] > cand_cap) { c->err = "beast decode: more candidates than the stream can hold"; rc = MGPU_E_OVERFLOW; }   // (cannot happen: beast_in_max_msgs)
-    // (every handler call's class is stored, by k_beast_in_classify or by the filter passes: nothing to zero)
-    if (int rc2 = filter_passes_end(c, p, r, rc ? 0 : total[1], 0, misc, adds)) return rc2;
-    if (rc) return rc;
-    n->frames = total[0]; n->msgs = misc[10]; n->id = total[8];
-    uint64_t garbage = total[2];
-    if (total[6] != ~0ull) {
-        const uint64_t at = total[6] >> 8, delta = (total[6] >> 3) & 31u;
-        n->stop = (total[6] & 7u) == BEAST_IN_STOP_SYNTH ? MGPU_BEAST_STOP_SYNTH : MGPU_BEAST_STOP_UUID;
-        n->consumed = at + delta;
-    } else {
-        n->consumed = total[7];
-        if (final && a.nbytes - n->consumed > kBeastInTail) {   // net_io.c:5010-5015
-            garbage += a.nbytes - n->consumed;
-            n->consumed = a.nbytes;
-        }
-    }
-    n->stop_off = n->consumed;
-    n->cn[0] = misc[2] + misc[3] + misc[4] + misc[5] + misc[6];   // remote_received_modes: every Mode S frame that reached the decode
-    n->cn[1] = misc[1] + total[5];                              // remote_received_modeac: the records, and the frames dropped with mode_ac off
-    for (int k = 2; k < 7; ++k) n->cn[k] = misc[k];
-    n->cn[7] = garbage; n->cn[8] = total[4]; n->cn[9] = total[3];
-    return MGPU_OK;
-}
-
-static int beast_decode_dev(mgpu_ctx *c, const struct mgpu_beast_in_args &a, uint64_t frame_base, uint64_t off_base, bool final, BeastInCounts *n, std::vector<uint32_t> *adds) {
-    return filter_tables_after(c, beast_decode_passes(c, a, frame_base, off_base, final, n, adds));
-}
-
-static bool beast_in_args_ok(const struct mgpu_beast_in_args *a) {
-    if (!a || a->size < sizeof(struct mgpu_beast_in_args) || !a->consumed || !a->nframes || !a->nmsgs || !a->stop || !a->stop_off || !a->receiver_id_out || !a->counters) return false;
-    if (a->nbytes >= (1ull << 32) || a->msgs_cap > UINT64_MAX / sizeof(mgpu_msg) || a->frames_cap > UINT64_MAX / sizeof(uint64_t)) return false;
-    if (a->now_ms < 0 || a->now_ms >= 253402300800000ll) return false;
-    if (a->nbytes && !a->data) return false;
-    if ((a->msgs_cap && (!a->msgs || !a->receiver_id)) || (a->frames_cap && !a->frame_class && !a->frame_off)) return false;
-    return true;
-}
-
-static void beast_in_report(const struct mgpu_beast_in_args *a, const BeastInCounts &n) {
-    *a->consumed = n.consumed; *a->nframes = n.frames; *a->nmsgs = n.msgs; *a->stop = n.stop; *a->stop_off = n.stop_off; *a->receiver_id_out = n.id;
-    beast_in_counters_of(n, a->counters);
-}
-
-static int beast_in_finish(mgpu_ctx *c, const struct mgpu_beast_in_args *a, const BeastInCounts &n, const IcaoFilter::Snapshot &before, const std::vector<uint32_t> &adds) {
-    const char *overflow = n.msgs > a->msgs_cap ? "beast decode: more messages than the arrays hold" :
-                           (a->frame_class || a->frame_off) && n.frames > a->frames_cap ? "beast decode: more handler calls than the frame arrays hold" : nullptr;
-    return filter_call_end(c, overflow, before, adds);
-}
-
-int mgpu_beast_decode_device(mgpu_ctx *c, const struct mgpu_beast_in_args *a) {
-    if (!c || !beast_in_args_ok(a)) return MGPU_E_INVAL;
-    if (((uintptr_t) a->msgs | (uintptr_t) a->receiver_id | (uintptr_t) a->frame_of | (uintptr_t) a->signal_level | (uintptr_t) a->frame_off) & 7u) return MGPU_E_INVAL;
-    BeastInCounts n;
-    n.id = a->receiver_id_in;
-    beast_in_report(a, n);
-    if (a->nbytes == 0) return MGPU_OK;
-    { const int rc = drain(c); if (rc != MGPU_OK) return rc; }
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    IcaoFilter::Snapshot before;
-    c->resolver.filter().snapshot(before);
-    std::vector<uint32_t> adds;
-    if (int rc = beast_decode_dev(c, *a, 0, 0, true, &n, &adds)) { c->resolver.filter().restore(before); return rc; }
-    beast_in_report(a, n);
-    return beast_in_finish(c, a, n, before, adds);
-}
-
-int mgpu_beast_decode(mgpu_ctx *c, const struct mgpu_beast_in_args *a) {
-    if (!c || !beast_in_args_ok(a)) return MGPU_E_INVAL;
-    BeastInCounts all;
-    all.id = a->receiver_id_in;
-    beast_in_report(a, all);
-    if (a->nbytes == 0) return MGPU_OK;
-    { const int rc = drain(c); if (rc != MGPU_OK) return rc; }
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    Behind &b = *c->behind;
-    IcaoFilter::Snapshot before;
-    c->resolver.filter().snapshot(before);
-    std::vector<uint32_t> adds;
-    const bool want_frames = a->frame_class || a->frame_off;
-    size_t adds_before = 0;
-    IcaoFilter::Snapshot pass_before;
-    const int prc = stream_passes(a->nbytes, a->pass_bytes ? a->pass_bytes : kLineDefaultPass, false, all,
-        [&](uint64_t at, uint64_t nb, bool final, const BeastInCounts &so_far, BeastInCounts &n) -> int {
-            // what this pass may write: what the caller's arrays still hold, and no more than nb bytes can give
-            const uint64_t msg_room = a->msgs_cap > so_far.msgs ? std::min<uint64_t>(a->msgs_cap - so_far.msgs, beast_in_max_msgs(nb)) : 0;
-            const uint64_t frame_room = want_frames && a->frames_cap > so_far.frames ? std::min<uint64_t>(a->frames_cap - so_far.frames, beast_in_max_frames(nb)) : 0;
-            int rc;
-            if ((rc = b.d_stream.reserve(c, nb + 64)) || (rc = b.d_in_msgs.reserve(c, (msg_room + 1) * sizeof(mgpu_msg))) ||
-                (rc = b.d_bin_ids.reserve(c, (msg_room + 1) * sizeof(uint64_t))) || (rc = b.d_index_of.reserve(c, (msg_room + 1) * sizeof(uint64_t))) ||
-                (rc = b.d_in_signal.reserve(c, (msg_room + 1) * sizeof(double))) || (rc = b.d_in_class.reserve(c, frame_room + 1)) ||
-                (rc = b.d_bin_frame_off.reserve(c, (frame_room + 1) * sizeof(uint64_t)))) return rc;
-            struct mgpu_beast_in_args d = *a;
-            d.data = b.d_stream.as<uint8_t>(); d.nbytes = nb; d.receiver_id_in = so_far.id;
-            d.msgs = b.d_in_msgs.as<mgpu_msg>(); d.receiver_id = b.d_bin_ids.as<uint64_t>(); d.msgs_cap = msg_room;
-            d.frame_of = a->frame_of ? b.d_index_of.as<uint64_t>() : nullptr;
-            d.signal_level = a->signal_level ? b.d_in_signal.as<double>() : nullptr;
-            d.frame_class = a->frame_class ? b.d_in_class.as<uint8_t>() : nullptr;
-            d.frame_off = a->frame_off ? b.d_bin_frame_off.as<uint64_t>() : nullptr;
-            d.frames_cap = frame_room;
-            HIPCHK(c, hipMemcpyAsync(b.d_stream.p, a->data + at, nb, hipMemcpyHostToDevice, c->stream_aux));
-            adds_before = adds.size();
-            c->resolver.filter().snapshot(pass_before);
-            if ((rc = beast_decode_dev(c, d, so_far.frames, at, final, &n, &adds))) return rc;
-            // (the pass stored below its rooms only: the copies stay inside the caller's arrays)
-            const uint64_t nmsg = std::min<uint64_t>(n.msgs, msg_room), nfr = std::min<uint64_t>(n.frames, frame_room);
-            if (nmsg) HIPCHK(c, hipMemcpy(a->msgs + so_far.msgs, d.msgs, nmsg * sizeof(mgpu_msg), hipMemcpyDeviceToHost));
-            if (nmsg) HIPCHK(c, hipMemcpy(a->receiver_id + so_far.msgs, d.receiver_id, nmsg * sizeof(uint64_t), hipMemcpyDeviceToHost));
-            if (nmsg && a->frame_of) HIPCHK(c, hipMemcpy(a->frame_of + so_far.msgs, d.frame_of, nmsg * sizeof(uint64_t), hipMemcpyDeviceToHost));
-            if (nmsg && a->signal_level) HIPCHK(c, hipMemcpy(a->signal_level + so_far.msgs, d.signal_level, nmsg * sizeof(double), hipMemcpyDeviceToHost));
-            if (nfr && a->frame_class) HIPCHK(c, hipMemcpy(a->frame_class + so_far.frames, d.frame_class, nfr, hipMemcpyDeviceToHost));
-            if (nfr && a->frame_off) HIPCHK(c, hipMemcpy(a->frame_off + so_far.frames, d.frame_off, nfr * sizeof(uint64_t), hipMemcpyDeviceToHost));
-            return MGPU_OK;
-        },
-        [&] { c->resolver.filter().restore(pass_before); adds.resize(adds_before); });
-    if (prc != MGPU_OK) { c->resolver.filter().restore(before); return prc; }
-    beast_in_report(a, all);
-    return beast_in_finish(c, a, all, before, adds);
-}
-
-// ---- Planefinder input: readPlanefinder + decodePfMessage over a DLE-framed stream (pf_in_format.h, kernels/pf_in.inc) ----
-
-// a: data and the per-message / per-call arrays device pointers, the capacities what this stretch may store (frame_class and frame_off
-// indexed by this stretch's own handler calls); a.nbytes are framed, `look` bytes behind them are the stream's too; frame_base and
-// off_base are added to frame_of and frame_off.  The counts of this stretch; the filter moved on as in raw_decode_passes.
-static int pf_decode_passes(mgpu_ctx *c, const struct mgpu_pf_in_args &a, uint64_t look, uint64_t frame_base, uint64_t off_base, PfInCounts *n, std::vector<uint32_t> *adds) {
-    Behind &b = *c->behind;
-    const uint64_t cand_cap = pf_in_max_frames(a.nbytes);
-    PfInScratch w;
-    if (int rc = b.beast_in.reserve_pf(c, a.nbytes, &w)) return rc;
-    RawInParams p;
-    FilterGens r;
-    if (int rc = filter_passes_begin(c, cand_cap, p, r)) return rc;
-    p.text = a.data; p.nbytes = a.nbytes; p.now_ms = a.now_ms;
-    p.msgs = a.msgs; p.line_of = (unsigned long long *) a.frame_of; p.signal_level = a.signal_level; p.msgs_cap = a.msgs ? a.msgs_cap : 0;
-    p.line_class = a.frame_class; p.line_class_cap = a.frame_class ? a.frames_cap : 0; p.line_base = frame_base;
-    PfInParams q;
-    q.data = a.data; q.nbytes = a.nbytes; q.look = look; q.cfg = p.cfg;
-    q.frame_class = a.frame_class; q.frame_off = (unsigned long long *) a.frame_off; q.frames_cap = (a.frame_class || a.frame_off) ? a.frames_cap : 0; q.off_base = off_base;
-    launch_pf_in_front(q, p, w, c->stream_aux);
-    HIPCHK(c, hipGetLastError());
-    unsigned long long total[6];
-    HIPCHK(c, hipMemcpyAsync(total, w.total, sizeof total, hipMemcpyDeviceToHost, c->stream_aux));
-    HIPCHK(c, hipStreamSynchronize(c->stream_aux));
-    unsigned long long misc[16];
-    int rc = MGPU_OK;
-    if (total[1] > cand_cap) { c->err = "pf decode: more candidates than the stream can hold"; rc = MGPU_E_OVERFLOW; }   // (cannot happen: pf_in_max_frames)
-    // (every handler call's class is stored, by k_pf_in_classify or by the filter passes: nothing to zero)
-    if (int rc2 = filter_passes_end(c, p, r, rc ? 0 : total[1], 0, misc, adds)) return rc2;
-    if (rc) return rc;
-    n->frames = total[0]; n->msgs = misc[10]; n->consumed = total[4];
-    n->cn[0] = misc[2] + misc[3] + misc[4] + misc[5] + misc[6];   // remote_received_modes: every Mode S frame that reached the decode
-    for (int k = 1; k < 7; ++k) n->cn[k] = misc[k];
-    n->cn[7] = total[2]; n->cn[8] = total[3];
-    return MGPU_OK;
-}
-
-static int pf_decode_dev(mgpu_ctx *c, const struct mgpu_pf_in_args &a, uint64_t look, uint64_t frame_base, uint64_t off_base, PfInCounts *n, std::vector<uint32_t> *adds) {
-    return filter_tables_after(c, pf_decode_passes(c, a, look, frame_base, off_base, n, adds));
-}
-
-static bool pf_in_args_ok(const struct mgpu_pf_in_args *a) {
-    if (!a || a->size < sizeof(struct mgpu_pf_in_args) || !a->consumed || !a->nframes || !a->nmsgs || !a->counters) return false;
-    if (a->nbytes + a->look >= (1ull << 32) || a->msgs_cap > UINT64_MAX / sizeof(mgpu_msg) || a->frames_cap > UINT64_MAX / sizeof(uint64_t)) return false;
-    if (a->now_ms < 0 || a->now_ms >= 253402300800000ll) return false;
-    if (a->nbytes && !a->data) return false;
-    if ((a->msgs_cap && !a->msgs) || (a->frames_cap && !a->frame_class && !a->frame_off)) return false;
-    return true;
-}
-
-static void pf_in_report(const struct mgpu_pf_in_args *a, const PfInCounts &n) {
-    *a->consumed = n.consumed; *a->nframes = n.frames; *a->nmsgs = n.msgs;
-    pf_in_counters_of(n, a->counters);
-}
-
-static int pf_in_finish(mgpu_ctx *c, const struct mgpu_pf_in_args *a, const PfInCounts &n, const IcaoFilter::Snapshot &before, const std::vector<uint32_t> &adds) {
-    const char *overflow = n.msgs > a->msgs_cap ? "pf decode: more messages than the arrays hold" :
-                           (a->frame_class || a->frame_off) && n.frames > a->frames_cap ? "pf decode: more handler calls than the frame arrays hold" : nullptr;
-    return filter_call_end(c, overflow, before, adds);
-}
-
-int mgpu_pf_decode_device(mgpu_ctx *c, const struct mgpu_pf_in_args *a) {
-    if (!c || !pf_in_args_ok(a)) return MGPU_E_INVAL;
-    if (((uintptr_t) a->msgs | (uintptr_t) a->frame_of | (uintptr_t) a->signal_level | (uintptr_t) a->frame_off) & 7u) return MGPU_E_INVAL;
-    PfInCounts n;
-    pf_in_report(a, n);
-    if (a->nbytes == 0) return MGPU_OK;
-    { const int rc = drain(c); if (rc != MGPU_OK) return rc; }
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    IcaoFilter::Snapshot before;
-    c->resolver.filter().snapshot(before);
-    std::vector<uint32_t> adds;
-    if (int rc = pf_decode_dev(c, *a, a->look, 0, 0, &n, &adds)) { c->resolver.filter().restore(before); return rc; }
-    pf_in_report(a, n);
-    return pf_in_finish(c, a, n, before, adds);
-}
-
-int mgpu_pf_decode(mgpu_ctx *c, const struct mgpu_pf_in_args *a) {
-    if (!c || !pf_in_args_ok(a)) return MGPU_E_INVAL;
-    PfInCounts all;
-    pf_in_report(a, all);
-    if (a->nbytes == 0) return MGPU_OK;
-    { const int rc = drain(c); if (rc != MGPU_OK) return rc; }
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    Behind &b = *c->behind;
-    IcaoFilter::Snapshot before;
-    c->resolver.filter().snapshot(before);
-    std::vector<uint32_t> adds;
-    const bool want_frames = a->frame_class || a->frame_off;
-    size_t adds_before = 0;
-    IcaoFilter::Snapshot pass_before;
-    const int prc = stream_passes(a->nbytes, a->pass_bytes ? a->pass_bytes : kLineDefaultPass, false, all,
-        [&](uint64_t at, uint64_t nb, bool, const PfInCounts &so_far, PfInCounts &n) -> int {
-            // a pass frames nb bytes; the lookahead and the handler's reads may take kPfInReach more, which decide every frame that starts
-            // inside the pass; what the caller's arrays still hold, and no more than nb bytes can give
-            const uint64_t look = pf_in_look(a->nbytes + a->look, at, nb);
-            const uint64_t msg_room = a->msgs_cap > so_far.msgs ? std::min<uint64_t>(a->msgs_cap - so_far.msgs, pf_in_max_frames(nb)) : 0;
-            const uint64_t frame_room = want_frames && a->frames_cap > so_far.frames ? std::min<uint64_t>(a->frames_cap - so_far.frames, pf_in_max_frames(nb)) : 0;
-            int rc;
-            if ((rc = b.d_stream.reserve(c, nb + look + 64)) || (rc = b.d_in_msgs.reserve(c, (msg_room + 1) * sizeof(mgpu_msg))) ||
-                (rc = b.d_index_of.reserve(c, (msg_room + 1) * sizeof(uint64_t))) || (rc = b.d_in_signal.reserve(c, (msg_room + 1) * sizeof(double))) ||
-                (rc = b.d_in_class.reserve(c, frame_room + 1)) || (rc = b.d_bin_frame_off.reserve(c, (frame_room + 1) * sizeof(uint64_t)))) return rc;
-            struct mgpu_pf_in_args d = *a;
-            d.data = b.d_stream.as<uint8_t>(); d.nbytes = nb;
-            d.msgs = b.d_in_msgs.as<mgpu_msg>(); d.msgs_cap = msg_room;
-            d.frame_of = a->frame_of ? b.d_index_of.as<uint64_t>() : nullptr;
-            d.signal_level = a->signal_level ? b.d_in_signal.as<double>() : nullptr;
-            d.frame_class = a->frame_class ? b.d_in_class.as<uint8_t>() : nullptr;
-            d.frame_off = a->frame_off ? b.d_bin_frame_off.as<uint64_t>() : nullptr;
-            d.frames_cap = frame_room;
-            HIPCHK(c, hipMemcpyAsync(b.d_stream.p, a->data + at, nb + look, hipMemcpyHostToDevice, c->stream_aux));
-            adds_before = adds.size();
-            c->resolver.filter().snapshot(pass_before);
-            if ((rc = pf_decode_dev(c, d, look, so_far.frames, at, &n, &adds))) return rc;
-            // (the pass stored below its rooms only: the copies stay inside the caller's arrays)
-            const uint64_t nmsg = std::min<uint64_t>(n.msgs, msg_room), nfr = std::min<uint64_t>(n.frames, frame_room);
-            if (nmsg) HIPCHK(c, hipMemcpy(a->msgs + so_far.msgs, d.msgs, nmsg * sizeof(mgpu_msg), hipMemcpyDeviceToHost));
-            if (nmsg && a->frame_of) HIPCHK(c, hipMemcpy(a->frame_of + so_far.msgs, d.frame_of, nmsg * sizeof(uint64_t), hipMemcpyDeviceToHost));
-            if (nmsg && a->signal_level) HIPCHK(c, hipMemcpy(a->signal_level + so_far.msgs, d.signal_level, nmsg * sizeof(double), hipMemcpyDeviceToHost));
-            if (nfr && a->frame_class) HIPCHK(c, hipMemcpy(a->frame_class + so_far.frames, d.frame_class, nfr, hipMemcpyDeviceToHost));
-            if (nfr && a->frame_off) HIPCHK(c, hipMemcpy(a->frame_off + so_far.frames, d.frame_off, nfr * sizeof(uint64_t), hipMemcpyDeviceToHost));
-            return MGPU_OK;
-        },
-        [&] { c->resolver.filter().restore(pass_before); adds.resize(adds_before); });
-    if (prc != MGPU_OK) { c->resolver.filter().restore(before); return prc; }
-    pf_in_report(a, all);
-    return pf_in_finish(c, a, all, before, adds);
-}
+int mgpu_raw_decode_device(mgpu_ctx *c, const struct mgpu_raw_in_args *a) { return msg_in_call<RawIn>(c, a, false); }
+int mgpu_raw_decode(mgpu_ctx *c, const struct mgpu_raw_in_args *a) { return msg_in_call<RawIn>(c, a, true); }
+int mgpu_beast_decode_device(mgpu_ctx *c, const struct mgpu_beast_in_args *a) { return msg_in_call<BeastIn>(c, a, false); }
+int mgpu_beast_decode(mgpu_ctx *c, const struct mgpu_beast_in_args *a) { return msg_in_call<BeastIn>(c, a, true); }
+int mgpu_pf_decode_device(mgpu_ctx *c, const struct mgpu_pf_in_args *a) { return msg_in_call<PfIn>(c, a, false); }
+int mgpu_pf_decode(mgpu_ctx *c, const struct mgpu_pf_in_args *a) { return msg_in_call<PfIn>(c, a, true); }
 
 // ---- ASTERIX input: readAsterix + decodeAsterixMessage over a length-chained stream (asterix_in_format.h, kernels/asterix_in.inc) ----
 

@@ -11,25 +11,18 @@
 
 namespace mgpu {
 
-// the counts of a call or of one pass of it
-struct PfInCounts {
-    uint64_t frames = 0, consumed = 0, msgs = 0;
-    uint64_t cn[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};              // struct mgpu_pf_in_counters in its order
-    // for stream_passes (stream_passes.h, shared by mgpu_pf_decode over the device and the sequential walk with args->pass_bytes != 0):
-    // a stretch is cut at the som it reached; nothing stops a stream; a stretch that reaches no som (a frame longer than it) is the
-    // one that is repeated
-    bool stopped() const { return false; }
-    void add(const PfInCounts &n) {
-        frames += n.frames; msgs += n.msgs;
-        for (int k = 0; k < 9; ++k) cn[k] += n.cn[k];
-    }
-};
-
-inline void pf_in_counters_of(const PfInCounts &n, struct mgpu_pf_in_counters *k) {
-    k->remote_received_modes = n.cn[0]; k->remote_received_modeac = n.cn[1]; k->remote_rejected_unknown_icao = n.cn[2]; k->remote_rejected_bad = n.cn[3];
-    for (int i = 0; i < 3; ++i) k->remote_accepted[i] = n.cn[4 + i];
+// A call as the stretch it is and its counts to the caller (raw_in_host.h: MsgInStretch, MsgInCounts; a unit is a handler call).
+#pragma GCC visibility push(hidden)
+inline MsgInStretch pf_in_stretch(const struct mgpu_pf_in_args &a) {
+    return {a.data, a.nbytes, a.look, a.now_ms, a.msgs, nullptr, a.signal_level, a.frame_of, a.msgs_cap, a.frame_class, a.frame_off, a.frames_cap, 0, 0, true, 0, 0};
+}
+inline void pf_in_report(const struct mgpu_pf_in_args &a, const MsgInCounts &n) {
+    *a.consumed = n.consumed; *a.nframes = n.units; *a.nmsgs = n.msgs;
+    struct mgpu_pf_in_counters *k = a.counters;
+    msg_in_counters_of(n, k);
     k->nskipped = n.cn[7]; k->past_end = n.cn[8];
 }
+#pragma GCC visibility pop
 
 // what a pass stages behind its nb bytes: the handler's reach, as far as the stream (args->nbytes + args->look bytes) goes
 inline uint64_t pf_in_look(uint64_t total, uint64_t at, uint64_t nb) { return total - at - nb < kPfInReach ? total - at - nb : kPfInReach; }

@@ -264,34 +264,13 @@ def have_ref_full():
 def build_ref_harness(workdir):
     """tests/host_stub/beast_in_ref_harness.c compiled with the flags of `make -C oracle full` and linked against that build's other
     objects, readsb.o with its main renamed in a copy (as tests/raw_in_util.py builds its harness)."""
-    exe = os.path.join(workdir, "beast_in_ref_harness")
-    main_o = os.path.join(workdir, "readsb_nomain_beast_in.o")
-    subprocess.run(["objcopy", "--redefine-sym", "main=readsb_main", os.path.join(sbs_util.REF_FULL, "readsb.o"), main_o], check=True)
-    objs, flags = sbs_util._full_build()
-    subprocess.run(["gcc", *flags, "-I" + os.path.join(helpers.ORACLE_DIR, "stub_full"), "-I/root/reference", "-I" + os.path.join(helpers.ROOT, "include"), HARNESS_SRC,
-                    main_o, *[os.path.join(sbs_util.REF_FULL, o + ".o") for o in objs], "-o", exe, "-pthread", "-lpthread", "-lm", "-lrt", "-l:libzstd.so.1", "-lz"],
-                   check=True)
-    return exe
+    return ru.build_ref_harness(workdir, "beast_in", HARNESS_SRC)
 
 
 def parse_results(blob, n):
     """n results as the harness writes them -> [dict(head, cls, off, frame_of, ids, signal, msgs)]"""
-    out, at = [], 0
-
-    def take(count, dtype):
-        nonlocal at
-        size = count * np.dtype(dtype).itemsize
-        v = np.frombuffer(blob[at: at + size], dtype=dtype).copy()
-        at += size
-        return v
-
-    for _ in range(n):
-        head = take(12, np.uint64)
-        nf, m = int(head[1]), int(head[2])
-        out.append(dict(head=head, cls=take(nf, np.uint8), off=take(nf, np.uint64), frame_of=take(m, np.uint64), ids=take(m, np.uint64), signal=take(m, np.float64),
-                        msgs=take(m, MSG)))
-    assert at == len(blob)
-    return out
+    return ru.read_results(blob, n, 12, (("cls", np.uint8), ("off", np.uint64)),
+                           (("frame_of", np.uint64), ("ids", np.uint64), ("signal", np.float64), ("msgs", MSG)))
 
 
 def run_ref_harness(exe, streams, cfg, workdir, ops=(), now_ms=NOW_MS, reps=1, id_in=ID_IN):
@@ -352,18 +331,11 @@ def host_decode(lib, stream, cfg, filt=None, now_ms=NOW_MS, id_in=ID_IN):
     """mgpu_beast_decode_host: the sequential walk.  cfg = (nfix_crc, fixDF, mode_ac, net_ingest); filt: a raw_in_util.FilterModel,
     moved on by the call."""
     from readsb_amd import binding
-    filt = filt if filt is not None else ru.FilterModel()
     buf = np.frombuffer(bytes(stream) + b"\xee", dtype=np.uint8)                             # (a byte behind the stream that nothing may read as the stream's)
     arrays, outs, cn = new_arrays(len(stream)), new_outs(), binding.BeastInCounters()
     a = beast_args(binding, buf.ctypes.data, len(stream), arrays, outs, cn, now_ms, id_in, cfg[3])
-    ga = np.zeros(len(filt.active) + len(stream) // 11 + 2, dtype=np.uint32)
-    ga[: len(filt.active)] = filt.active
-    gi = np.concatenate([np.array(sorted(filt.inactive), dtype=np.uint32), np.zeros(1, dtype=np.uint32)])
-    f = binding.RawInFilter(ga.ctypes.data, gi.ctypes.data, len(filt.active), len(filt.inactive), filt.occupied, filt.bits)
     kcfg = binding.RawInConfig(C.sizeof(binding.RawInConfig), *cfg[:3])
-    rc = int(lib.mgpu_beast_decode_host(C.byref(a), C.byref(kcfg), C.byref(f)))
-    if rc == MGPU_OK:
-        filt.active, filt.inactive, filt.occupied, filt.bits = [int(x) for x in ga[: f.n_active]], set(int(x) for x in gi[: f.n_inactive]), int(f.occupied), int(f.table_bits)
+    rc = ru.through_filter(filt, len(stream) // 11 + 2, lambda f: lib.mgpu_beast_decode_host(C.byref(a), C.byref(kcfg), f))
     return result_of(binding, rc, arrays, outs, cn)
 
 

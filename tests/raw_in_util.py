@@ -358,37 +358,45 @@ def have_ref_full():
     return sbs_util.have_ref_full()
 
 
-def build_ref_harness(workdir):
-    """tests/host_stub/raw_in_ref_harness.c compiled with the flags of `make -C oracle full` and linked against that build's other
-    objects, readsb.o with its main renamed in a copy (as tests/sbs_in_util.py builds its harness)."""
-    exe = os.path.join(workdir, "raw_in_ref_harness")
-    main_o = os.path.join(workdir, "readsb_nomain_raw_in.o")
+def build_ref_harness(workdir, name="raw_in", src=HARNESS_SRC):
+    """A message input's harness (tests/host_stub/<name>_ref_harness.c; beast_in_util and pf_in_util build theirs here) compiled with
+    the flags of `make -C oracle full` and linked against that build's other objects, readsb.o with its main renamed in a copy (as
+    tests/sbs_in_util.py builds its harness)."""
+    exe = os.path.join(workdir, name + "_ref_harness")
+    main_o = os.path.join(workdir, "readsb_nomain_%s.o" % name)
     subprocess.run(["objcopy", "--redefine-sym", "main=readsb_main", os.path.join(sbs_util.REF_FULL, "readsb.o"), main_o], check=True)
     objs, flags = sbs_util._full_build()
-    subprocess.run(["gcc", *flags, "-I" + os.path.join(helpers.ORACLE_DIR, "stub_full"), "-I/root/reference", "-I" + os.path.join(helpers.ROOT, "include"), HARNESS_SRC,
+    subprocess.run(["gcc", *flags, "-I" + os.path.join(helpers.ORACLE_DIR, "stub_full"), "-I/root/reference", "-I" + os.path.join(helpers.ROOT, "include"), src,
                     main_o, *[os.path.join(sbs_util.REF_FULL, o + ".o") for o in objs], "-o", exe, "-pthread", "-lpthread", "-lm", "-lrt", "-l:libzstd.so.1", "-lz"],
                    check=True)
     return exe
 
 
-def parse_results(blob, n):
-    """n results as the harness writes them -> [dict(head, line_of, signal, msgs)]"""
+def read_results(blob, n, nhead, unit_fields, msg_fields):
+    """n results as a message input's harness writes them: nhead 64-bit words (the second counts the units — lines, handler calls —,
+    the third the messages), the per-unit arrays, the per-message arrays; the fields as ((name, dtype), ...) -> [dict(head, names...)]"""
     out, at = [], 0
+
+    def take(count, dtype):
+        nonlocal at
+        size = count * np.dtype(dtype).itemsize
+        v = np.frombuffer(blob[at: at + size], dtype=dtype).copy()
+        at += size
+        return v
+
     for _ in range(n):
-        head = np.frombuffer(blob[at: at + 80], dtype=np.uint64).copy()
-        at += 80
-        m = int(head[2])
-        cls = np.frombuffer(blob[at: at + int(head[1])], dtype=np.uint8).copy()
-        at += int(head[1])
-        line_of = np.frombuffer(blob[at: at + 8 * m], dtype=np.uint64).copy()
-        at += 8 * m
-        signal = np.frombuffer(blob[at: at + 8 * m], dtype=np.float64).copy()
-        at += 8 * m
-        msgs = np.frombuffer(blob[at: at + 64 * m], dtype=MSG).copy()
-        at += 64 * m
-        out.append(dict(head=head, cls=cls, line_of=line_of, signal=signal, msgs=msgs))
+        r = dict(head=take(nhead, np.uint64))
+        for count, fields in ((int(r["head"][1]), unit_fields), (int(r["head"][2]), msg_fields)):
+            for name, dtype in fields:
+                r[name] = take(count, dtype)
+        out.append(r)
     assert at == len(blob)
     return out
+
+
+def parse_results(blob, n):
+    """n results as the harness writes them -> [dict(head, cls, line_of, signal, msgs)]"""
+    return read_results(blob, n, 10, (("cls", np.uint8),), (("line_of", np.uint64), ("signal", np.float64), ("msgs", MSG)))
 
 
 def run_ref_harness(exe, streams, cfg, workdir, ops=(), now_ms=NOW_MS, reps=1):
@@ -421,11 +429,25 @@ def ops_of(group):
 
 # ---- the library's host side ----
 
+def through_filter(filt, room, call):
+    """A sequential walk of the library's (mgpu_raw_decode_host and its like) against a FilterModel: call(a reference to the
+    binding.RawInFilter that holds filt, with room for `room` new adds) -> its rc; filt is moved on unless the walk failed."""
+    from readsb_amd import binding
+    filt = filt if filt is not None else FilterModel()
+    ga = np.zeros(len(filt.active) + room, dtype=np.uint32)
+    ga[: len(filt.active)] = filt.active
+    gi = np.concatenate([np.array(sorted(filt.inactive), dtype=np.uint32), np.zeros(1, dtype=np.uint32)])
+    f = binding.RawInFilter(ga.ctypes.data, gi.ctypes.data, len(filt.active), len(filt.inactive), filt.occupied, filt.bits)
+    rc = int(call(C.byref(f)))
+    if rc == MGPU_OK:
+        filt.active, filt.inactive, filt.occupied, filt.bits = [int(x) for x in ga[: f.n_active]], set(int(x) for x in gi[: f.n_inactive]), int(f.occupied), int(f.table_bits)
+    return rc
+
+
 def host_decode(lib, stream, cfg, filt=None, now_ms=NOW_MS):
     """mgpu_raw_decode_host: the sequential resolver.  filt: a FilterModel, moved on by the call.
     -> dict(rc, consumed, nlines, nmsgs, counters, msgs, line_of, signal, cls)"""
     from readsb_amd import binding
-    filt = filt if filt is not None else FilterModel()
     buf = np.frombuffer(bytes(stream) + b"\n", dtype=np.uint8)
     nl = len(stream) + 1
     cap = len(stream) // 6 + 1
@@ -434,15 +456,8 @@ def host_decode(lib, stream, cfg, filt=None, now_ms=NOW_MS):
     cn = binding.RawInCounters()
     a = binding.RawInArgs(C.sizeof(binding.RawInArgs), 0, buf.ctypes.data, len(stream), now_ms, msgs.ctypes.data, line_of.ctypes.data, signal.ctypes.data, cap, cls.ctypes.data, nl,
                           *[C.pointer(x) for x in c], C.pointer(cn), 0)
-    ga = np.zeros(len(filt.active) + nl, dtype=np.uint32)
-    ga[: len(filt.active)] = filt.active
-    gi = np.array(sorted(filt.inactive), dtype=np.uint32)
-    gi = np.concatenate([gi, np.zeros(1, dtype=np.uint32)])
-    f = binding.RawInFilter(ga.ctypes.data, gi.ctypes.data, len(filt.active), len(filt.inactive), filt.occupied, filt.bits)
     kcfg = binding.RawInConfig(C.sizeof(binding.RawInConfig), *cfg)
-    rc = int(lib.mgpu_raw_decode_host(C.byref(a), C.byref(kcfg), C.byref(f)))
-    if rc == MGPU_OK:
-        filt.active, filt.inactive, filt.occupied, filt.bits = [int(x) for x in ga[: f.n_active]], set(int(x) for x in gi[: f.n_inactive]), int(f.occupied), int(f.table_bits)
+    rc = through_filter(filt, nl, lambda f: lib.mgpu_raw_decode_host(C.byref(a), C.byref(kcfg), f))
     n = int(c[2].value)
     return dict(rc=rc, consumed=int(c[0].value), nlines=int(c[1].value), nmsgs=n, counters=[int(cn.remote_received_modes), int(cn.remote_received_modeac),
                 int(cn.remote_rejected_unknown_icao), int(cn.remote_rejected_bad), *[int(x) for x in cn.remote_accepted]],
